@@ -10,7 +10,10 @@ BERT-base + ViT-B/16 patches (196 per image, 393 vision tokens), bf16 compute, b
     python bench.py --gpus 1 --steps 10 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         bench.py --gpus 8 --steps 10 --warmup 3
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the headline; ``--full`` adds everything
+else the line can carry (kernel roofline, evaluation passes, reference parity, the side legs, the CPU baseline, the replica check).
+``--dump-outputs DIR`` writes what the last timed step handed its caller (the loss and a fixed, seeded sample of the updated weights)
+as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -302,10 +305,12 @@ class PowerSampler:
     """Package power and shader clock of GPU ``index`` sampled from a helper thread while a timed region runs (rocm-smi, a few Hz; a separate
     process per sample, so the launching thread is not slowed).  ``median()`` -> (W, MHz, n) or (None, None, 0) where the tool is absent."""
 
-    def __init__(self, index: int = 0):
+    def __init__(self, index: int = 0, active: bool = True):
         import shutil
         self.index, self.samples, self._stop, self._th = index, [], False, None
         self.tool = shutil.which("rocm-smi") or ("/opt/rocm/bin/rocm-smi" if os.path.exists("/opt/rocm/bin/rocm-smi") else None)
+        if not active:
+            self.tool = None
 
     def _run(self):
         import re
@@ -366,6 +371,28 @@ def timed_leg(tr, lit, batch, n_warm: int, n_steps: int, barrier, first_idx: int
     return dt
 
 
+def dump_outputs(out_dir: str, model, loss, seed: int = 0) -> None:
+    """What the timed step hands its caller, written after the last timed step: ``loss.npy`` (the loss that step returned) and
+    ``weights_sample.npy`` (the parameters as its AdamW update left them, float32).  Parameters of up to 4096 elements go in whole,
+    larger ones as a fixed, seeded sample of 1/64 of their elements (~14 MB for the headline network), in named_parameters() order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    parts = []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            flat = p.detach().reshape(-1)
+            n = flat.numel()
+            if n <= 4096:
+                parts.append(flat.float())
+            else:
+                idx = np.sort(rng.choice(n, size=n // 64, replace=False))
+                parts.append(flat[torch.from_numpy(idx).to(flat.device)].float())
+        w = torch.cat(parts).cpu().numpy()
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(loss.detach().float().cpu().numpy(), dtype=np.float32).reshape(1))
+    np.save(os.path.join(out_dir, "weights_sample.npy"), w.astype(np.float32, copy=False))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -392,6 +419,12 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--train-only", action="store_true", help="skip the evaluation pass (Hits@1), the precision comparison and the alternate-head run: "
                                                               "the process then launches nothing but training steps (rocprofv3 traces whose per-kernel averages are per training step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: kernel roofline and power, evaluation passes, reference parity, the "
+                         "side legs (other head, weights, precision, geometry, length, task, model), the CPU baseline, communication and replica checks "
+                         "(the --no-* / --train-only flags above leave parts of it out); without it the run only sets up, warms up and times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy (loss, seeded weight sample)")
     a = ap.parse_args()
     if a.cpu_rate_only:
         print(cpu_step_rate(a.patch, a.seq_len, a.cpu_rate_only, a.cpu_iters), flush=True)
@@ -411,6 +444,8 @@ def main():
         raise SystemExit(f"bench.py: --gpus {a.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {a.gpus}, "
                          f"or run `python bench.py --gpus {a.gpus}` without WORLD_SIZE / RANK in the environment (it then starts its own ranks)")
     ops.require_gpu()
+    if not a.full:                                   # a plain run: the headline alone -- every leg after the timed steps belongs to --full
+        a.no_kernel_timing = a.train_only = a.no_cpu_baseline = True
     dev = torch.device("cuda", local)
     pre = a.task == "pretrain"
     if a.weights is None:
@@ -439,7 +474,7 @@ def main():
     tr.settle_pool()                                 # (--warmup < 3: the allocator's pool headroom now, not inside the timed steps)
     barrier()
     allocs0 = device_allocs()
-    with PowerSampler(local) as psamp:               # (helper thread; rank 0 reports it)
+    with PowerSampler(local, active=a.full) as psamp:  # (helper thread; rank 0 reports it)
         t0 = time.perf_counter()
         for i in range(a.steps):
             loss = tr.train_step(lit, batch, a.warmup + i)
@@ -455,6 +490,8 @@ def main():
     P = (224 // a.patch) ** 2
     value = a.batch * world * a.steps / dt
     train_gflop = 3.0 * (fwd_gflop_per_example(P, a.seq_len, head) if a.model == "mkgformer" else flava_fwd_gflop_per_example(P, a.seq_len, head))
+    if a.dump_outputs and rank == 0:                 # before any leg below takes another step or loads other weights
+        dump_outputs(a.dump_outputs, model, loss)
 
     roof = None
     if not a.no_kernel_timing:
@@ -683,7 +720,7 @@ def main():
         altt = leg("mkgformer", True, 96, "BASELINE configs[4]: MarKG pre-train step (link prediction), L = 96, heads E = 11292 / R = 192, pre_type 50/50, no sep_idx")
         altm = leg("flava", False, a.seq_len, "BASELINE configs[3]: FLAVA-base backbone (12 image + 12 text + 6 multimodal layers, 393 image tokens), fine-tune step")
     spread = None
-    if world > 1:
+    if world > 1 and a.full:
         # data-parallel self-check: every replica must hold the same weights after the same all-reduced updates
         cs = model.store.master.double().sum().reshape(1)
         hi, lo = cs.clone(), cs.clone()
@@ -736,12 +773,13 @@ def main():
             out["comm"] = comm
             out["comm_exposed_ms"] = comm["comm_exposed_ms"]
             out["rccl_world"] = comm["rccl_world"]
-        try:                                            # bad labels / examples without [MASK] flagged by any kernel of this process (functional.check_status)
-            from mkg_analogy_amd import functional as Fn_
-            Fn_.check_status()
-            out["status_check"] = "ok"
-        except IndexError as e:
-            out["status_check"] = f"FLAGGED: {e}"
+        if a.full:
+            try:                                        # bad labels / examples without [MASK] flagged by any kernel of this process (functional.check_status)
+                from mkg_analogy_amd import functional as Fn_
+                Fn_.check_status()
+                out["status_check"] = "ok"
+            except IndexError as e:
+                out["status_check"] = f"FLAGGED: {e}"
         out["metric_detail"] = f"entity_head={head}, text_f16={int(getattr(getattr(model, 'engine', None), 'text_f16', False))}, weights={a.weights}"
         if not a.no_cpu_baseline and world == 1 and a.model == "mkgformer" and not pre:
             try:

@@ -18,7 +18,7 @@ def test_bench_two_ranks_share_one_gpu():
     env = dict(os.environ, MART_DIST_BACKEND="gloo", MART_DEVICE_INDEX="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "32",
-           "--patch", "32", "--no-cpu-baseline", "--no-kernel-timing"]
+           "--patch", "32", "--no-cpu-baseline", "--no-kernel-timing", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -39,7 +39,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "LOCAL_WORLD_SIZE", "GROUP_RANK")}
     env.update(MART_DIST_BACKEND="gloo", MART_DEVICE_INDEX="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16", "--patch", "32",
-           "--no-cpu-baseline", "--no-kernel-timing", "--train-only"]
+           "--no-cpu-baseline", "--no-kernel-timing", "--train-only", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
