@@ -196,6 +196,32 @@ int mart_text_embed_scatter(const float* ds, const int64_t* ids, const int64_t* 
 int mart_text_embed_scatter_det(const float* ds, const int64_t* ids, const int64_t* tt, const int64_t* order, float* dword, float* dpos, float* dtype,
                                 int B, int L, int H, float* ws, long long ws_bytes, int32_t* meta, void* stream);
 
+/* ---------------------------------------------------------------- ViLT joint embedding (modeling_vilt.py:199-300, csrc/vilt.hip)
+ * Joint stream x [B*S, H] f32, S = L + 2 (1 + P), text first, then two images of [cls | P patch tokens]:
+ *   text t        : LayerNorm(word[id] + ttype[tt] + (t < n_tpos ? tpos[t] : 0)) + modality[0]
+ *   image i, j = 0: cls + ipos[0] + modality[1];  j >= 1: patch(b, i, perm[i][b][j-1]) + ipos[1 + perm[..]] + modality[1]
+ * patch rows are (b*2 + i)*P + q (the patch-projection GEMM output, f32 or bf16); perm / inv are int32 [2, B, P] (inv = the inverse
+ * permutation).  Backward (deterministic, no float atomics): ds_text = d(LayerNorm input) [B*L, H] (the word-row scatter's operand),
+ * dpatch bf16 [B*2*P, H] un-permuted, and dgamma, dbeta, dtpos[:n_tpos], dttype[2], dcls, dipos[1+P], dmodality[2] ACCUMULATED (+=).
+ * ws: (1 + P + 4 L) * H floats.  H % 256 == 0, H <= 1024. */
+typedef struct {
+  const int64_t* ids; const int64_t* tt;                            /* [B, L] */
+  const float* word; const float* tpos; const float* ttype;          /* text tables; tpos has n_tpos rows */
+  const float* gamma; const float* beta; float eps; int n_tpos;
+  const float* patch_f32; const void* patch_bf16;                   /* exactly one (forward) */
+  const float* cls; const float* ipos; const float* modality;        /* [H], [1+P, H], [2, H] */
+  const int32_t* perm; const int32_t* inv;                          /* [2, B, P] */
+  int B, L, P, H;
+  float* x;                                                         /* forward output [B*S, H] */
+  float* s_text; float* mean; float* rstd;                          /* LayerNorm input [B*L, H] and statistics [B*L]: written forward, read backward */
+  const float* dx;                                                  /* backward input [B*S, H] */
+  float* ds_text; void* dpatch;
+  float* dgamma; float* dbeta; float* dtpos; float* dttype; float* dcls; float* dipos; float* dmodality;
+  float* ws; long long ws_bytes;
+} mart_vilt_embed_desc;
+int mart_vilt_embed_fwd(const mart_vilt_embed_desc* d, void* stream);
+int mart_vilt_embed_bwd(const mart_vilt_embed_desc* d, void* stream);
+
 /* ---------------------------------------------------------------- attention (head_dim 64)
  * Flash-style multi-head attention, K/V tiles staged in LDS, wave-level online softmax.
  *  vision: CLIPAttention.forward, modeling_unimo.py:212-272 -- no mask, keys = [text prefix (K,V) | own]
@@ -216,6 +242,8 @@ typedef struct {
   float* lse;                                                       /* [B,nh,Sq] softmax statistic, LOG2 domain: log2(sum_j 2^(s_ij*log2e)) */
   int rw_skip_row0;                                                 /* FLAVA reweight variant: query row 0 ([CLS]) is not scaled (modeling_flava.py:494) */
   void* ctx_f16;                                                    /* optional: the context also as fp16 (rounded once from f32; ld = ldctx): A operand of the fp16 output projection */
+  int rw_row_lo;                                                    /* ViLT reweight variant (modeling_vilt.py:370-375): query rows below max(rw_row_lo, rw_skip_row0) keep
+                                                                       factor 1; 0 = off.  Runs on the two-pass text kernels (any Sq / Sk) */
 } mart_attn_fwd_desc;
 int mart_attn_fwd(const mart_attn_fwd_desc* d, void* stream);
 
@@ -386,6 +414,8 @@ typedef struct {
                                                                       (three products, 2^-16 relative: the arithmetic of the path's GEMMs) instead of exact f32 */
   void* ctx_split3; long long ldctx3;                              /* optional, fast path only: the context ALSO as [hi | lo | hi] bf16 rows of 3 * nh * D columns
                                                                       (row stride ldctx3 elements): the A operand of the output projection, no separate split pass */
+  int rw_row_lo;                                                   /* ViLT reweight variant (as mart_attn_fwd_desc): query rows below max(rw_row_lo, rw_skip_row0) keep
+                                                                      factor 1; 0 = off.  Forward, D = 64, 16-byte aligned operands only (the backward refuses it) */
 } mart_attn_f32_desc;
 int mart_attn_fwd_f32(const mart_attn_f32_desc* d, void* stream);
 

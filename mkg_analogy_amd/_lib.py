@@ -59,7 +59,8 @@ class AttnFwd(C.Structure):
                 ("pk", vp), ("pv", vp), ("ldp", i32), ("Lp", i32),
                 ("B", i32), ("nh", i32), ("Sq", i32), ("Sk", i32), ("scale", f32),
                 ("attn_mask", vp), ("sep", vp), ("sep_stride", i32), ("w0", vp), ("w1", vp),
-                ("p_drop", f32), ("seed", u64), ("ctx", vp), ("ldctx", i32), ("lse", vp), ("rw_skip_row0", i32), ("ctx_f16", vp)]
+                ("p_drop", f32), ("seed", u64), ("ctx", vp), ("ldctx", i32), ("lse", vp), ("rw_skip_row0", i32), ("ctx_f16", vp),
+                ("rw_row_lo", i32)]
 
 
 class AttnF32(C.Structure):
@@ -67,7 +68,8 @@ class AttnF32(C.Structure):
                 ("pk", vp), ("pv", vp), ("ldp", i64), ("Lp", i32),
                 ("B", i32), ("nh", i32), ("D", i32), ("Sq", i32), ("Sk", i32), ("scale", f32),
                 ("attn_mask", vp), ("sep", vp), ("sep_stride", i32), ("w0", vp), ("w1", vp), ("rw_skip_row0", i32),
-                ("ctx", vp), ("ldctx", i64), ("fast", i32), ("ctx_split3", vp), ("ldctx3", i64)]
+                ("ctx", vp), ("ldctx", i64), ("fast", i32), ("ctx_split3", vp), ("ldctx3", i64),
+                ("rw_row_lo", i32)]
 
 
 class AttnBwdF32(C.Structure):
@@ -79,6 +81,14 @@ class AttnBwd(C.Structure):
     _fields_ = [("f", AttnFwd), ("dctx", vp), ("lddctx", i32), ("delta", vp),
                 ("dq", vp), ("dk", vp), ("dv", vp), ("lddq", i32), ("lddk", i32), ("lddv", i32),
                 ("dpk", vp), ("dpv", vp), ("lddp", i32), ("accum_dkv", i32), ("dw", vp), ("dw_ws", vp)]
+
+
+class ViltEmbed(C.Structure):
+    _fields_ = [("ids", vp), ("tt", vp), ("word", vp), ("tpos", vp), ("ttype", vp), ("gamma", vp), ("beta", vp), ("eps", f32), ("n_tpos", i32),
+                ("patch_f32", vp), ("patch_bf16", vp), ("cls", vp), ("ipos", vp), ("modality", vp), ("perm", vp), ("inv", vp),
+                ("B", i32), ("L", i32), ("P", i32), ("H", i32), ("x", vp), ("s_text", vp), ("mean", vp), ("rstd", vp),
+                ("dx", vp), ("ds_text", vp), ("dpatch", vp), ("dgamma", vp), ("dbeta", vp), ("dtpos", vp), ("dttype", vp),
+                ("dcls", vp), ("dipos", vp), ("dmodality", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
 class FusionFwd(C.Structure):
@@ -165,6 +175,8 @@ _SIGS = {
     "mart_patchify_f32": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "mart_vision_assemble_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "mart_attn_fwd_f32": (i32, [vp, vp]),
+    "mart_vilt_embed_fwd": (i32, [C.POINTER(ViltEmbed), vp]),
+    "mart_vilt_embed_bwd": (i32, [C.POINTER(ViltEmbed), vp]),
 }
 
 EXPORTS = tuple(_SIGS)

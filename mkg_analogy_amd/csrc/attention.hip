@@ -267,31 +267,36 @@ struct TextCtl {                          // per-(b) text controls, all optional
   float p_drop, inv_keep; uint64_t seed;
   uint32_t s2, thr;                       // dropout: folded seed and 16-bit threshold (common.h: dropout_keep32)
 };
+// LO (ViLT, rw_row_lo > 0): skip0 holds the first reweighted query row, max(rw_row_lo, rw_skip_row0); rows below it keep factor 1.
+// The LO = false instantiations are the kernels as they were (the field is not read).
+template <bool LO = false>
 __device__ __forceinline__ TextCtl make_ctl(const mart_attn_fwd_desc& p, int b, int Sk) {
   TextCtl c;
   c.mask_row = p.attn_mask ? p.attn_mask + (long long)b * Sk : nullptr;
   c.sep = p.sep ? (int)p.sep[(long long)b * p.sep_stride] : -1;
-  c.skip0 = p.rw_skip_row0;
+  c.skip0 = LO ? (p.rw_row_lo > (p.rw_skip_row0 ? 1 : 0) ? p.rw_row_lo : (p.rw_skip_row0 ? 1 : 0)) : p.rw_skip_row0;
   c.c0 = p.w0 ? fminf(fmaxf(p.w0[0], 0.f), 0.5f) : 1.f;
   c.c1 = p.w1 ? fminf(fmaxf(p.w1[0], 0.5f), 1.f) : 1.f;
   c.p_drop = p.p_drop; c.inv_keep = 1.f / (1.f - p.p_drop); c.seed = p.seed;
   c.s2 = rng_seedmix(p.seed, 0); c.thr = dropout_thr16(p.p_drop);
   return c;
 }
+template <bool LO = false>
 __device__ __forceinline__ float reweight(const TextCtl& c, int qi, int kj) {
   if (c.sep < 0 || kj < c.sep) return 1.f;
   if (qi >= c.sep) return c.c1;
-  return (c.skip0 && qi == 0) ? 1.f : c.c0;
+  return (LO ? qi < c.skip0 : (c.skip0 && qi == 0)) ? 1.f : c.c0;
 }
 
 // Query-owner kernels (forward, dQ): everything about the adaptive reweight that depends on the QUERY is lane-constant -- the factor this
 // query applies to keys >= sep and the two selectors of the d(w0) / d(w1) sums -- so a score costs one compare + select instead of the
 // branches of reweight() (the per-score divergent `if`s compiled to ~80 s_and_saveexec in the text dQ kernel).
 struct QueryRw { float fq, sel0, sel1; int sep; };
+template <bool LO = false>
 __device__ __forceinline__ QueryRw make_qrw(const TextCtl& c, int qi) {
   QueryRw q;
   q.sep = c.sep < 0 ? 0x7fffffff : c.sep;                    // no reweight: no key is >= sep
-  const bool hi = qi >= q.sep, lo_ok = !hi && !(c.skip0 && qi == 0);
+  const bool hi = qi >= q.sep, lo_ok = !hi && (LO ? qi >= c.skip0 : !(c.skip0 && qi == 0));
   q.fq = hi ? c.c1 : (lo_ok ? c.c0 : 1.f);
   q.sel1 = hi ? 1.f : 0.f; q.sel0 = lo_ok ? 1.f : 0.f;
   return q;
@@ -332,7 +337,7 @@ constexpr int RES_NTH = 1024;
 #define FWD_NW 4                         // waves per workgroup of the vision ring kernel (one query tile each); waves 0-3 stage the K / V tiles
 #endif
 constexpr int fwd_waves(bool text, int tpw, bool res) { return (!text && tpw == 1 && !res) ? FWD_NW : 4; }
-template <bool TEXT, int TPW, bool RES = false>
+template <bool TEXT, int TPW, bool RES = false, bool LO = false>
 __global__ __launch_bounds__(RES ? RES_NTH : 64 * fwd_waves(TEXT, TPW, RES), RES ? 1 : ((TPW == 1 && !TEXT) ? ATTN_FWD_MINW1 : 2)) void attn_fwd_k(mart_attn_fwd_desc p) {
   constexpr int NWV = fwd_waves(TEXT, TPW, RES);
   static_assert(!RES || (TPW == 1 && !TEXT), "the resident form is the vision kernel, one query tile per wave");
@@ -344,7 +349,7 @@ __global__ __launch_bounds__(RES ? RES_NTH : 64 * fwd_waves(TEXT, TPW, RES), RES
   const int Stot = p.Lp + p.Sk;
   const Side K{(const bf16*)p.k, p.ldk, p.Sk, (const bf16*)p.pk, p.ldp, p.Lp};
   const Side V{(const bf16*)p.v, p.ldv, p.Sk, (const bf16*)p.pv, p.ldp, p.Lp};
-  const TextCtl ctl = make_ctl(p, b, p.Sk);
+  const TextCtl ctl = make_ctl<LO>(p, b, p.Sk);
   constexpr bool text = TEXT;          // vision instantiation: no mask / reweight / dropout code at all
   const bool stamp_on = !TEXT && !RES && b == p.B / 2 && h == 5 && wg.part == 1;
   ATTN_STAMP(0, stamp_on, 0);
@@ -589,7 +594,7 @@ __global__ __launch_bounds__(RES ? RES_NTH : 64 * fwd_waves(TEXT, TPW, RES), RES
       } else {
         float mx = -1.0e30f;
         const uint64_t mb = mask_bits(ctl, kt, Stot, lane) >> (4 * hh);   // this lane's keys: bit (t*32 + (r&3) + 8*(r>>2))
-        const QueryRw qr = make_qrw(ctl, qi[u]);
+        const QueryRw qr = make_qrw<LO>(ctl, qi[u]);
 #pragma unroll
         for (int t = 0; t < 2; ++t) if (t < NT)
 #pragma unroll
@@ -797,7 +802,7 @@ __global__ __launch_bounds__(RES ? RES_NTH : 64 * fwd_waves(TEXT, TPW, RES), RES
 
 // =========================================================================== backward, dQ pass (owner = queries)
 // TPW query tiles per wave as in the forward kernel (two independent exp / dS chains per wave, half the K/V streams).
-template <bool TEXT, int TPW>
+template <bool TEXT, int TPW, bool LO = false>
 __global__ __launch_bounds__(NTH) void attn_bwd_dq_k(mart_attn_bwd_desc pb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mart_attn_fwd_desc& p = pb.f;
@@ -808,7 +813,7 @@ __global__ __launch_bounds__(NTH) void attn_bwd_dq_k(mart_attn_bwd_desc pb) {
   const int Stot = p.Lp + p.Sk;
   const Side K{(const bf16*)p.k, p.ldk, p.Sk, (const bf16*)p.pk, p.ldp, p.Lp};
   const Side V{(const bf16*)p.v, p.ldv, p.Sk, (const bf16*)p.pv, p.ldp, p.Lp};
-  const TextCtl ctl = make_ctl(p, b, p.Sk);
+  const TextCtl ctl = make_ctl<LO>(p, b, p.Sk);
   constexpr bool text = TEXT;          // vision instantiation: no mask / reweight / dropout code at all
   const LaneOffs lo = make_offs(lane);
 
@@ -895,7 +900,7 @@ __global__ __launch_bounds__(NTH) void attn_bwd_dq_k(mart_attn_bwd_desc pb) {
           }
         } else {
           const uint64_t mb = mask_bits(ctl, kt, Stot, lane) >> (4 * hh);
-          const QueryRw qr = make_qrw(ctl, qi[u]);
+          const QueryRw qr = make_qrw<LO>(ctl, qi[u]);
           const uint32_t rowbase = (uint32_t)(((uint32_t)b * p.nh + h) * p.Sq + (uint32_t)qi[u]) * (uint32_t)Stot;
           const float lse_u = qvalid[u] ? lse[u] : 1.0e30f;    // rows past Sq: p = exp2(x - 1e30) = 0
 #pragma unroll
@@ -976,7 +981,7 @@ __global__ void attn_dw_reduce_k(const float* __restrict__ ws, long long n, cons
 }
 
 // =========================================================================== backward, dK/dV pass (owner = keys)
-template <bool TEXT>
+template <bool TEXT, bool LO = false>
 __global__ __launch_bounds__(NTH, 2) void attn_bwd_dkv_k(mart_attn_bwd_desc pb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mart_attn_fwd_desc& p = pb.f;
@@ -990,7 +995,7 @@ __global__ __launch_bounds__(NTH, 2) void attn_bwd_dkv_k(mart_attn_bwd_desc pb) 
   const Side V{(const bf16*)p.v, p.ldv, p.Sk, (const bf16*)p.pv, p.ldp, p.Lp};
   const Side Q{(const bf16*)p.q, p.ldq, p.Sq, nullptr, 0, 0};
   const Side G{(const bf16*)pb.dctx, pb.lddctx, p.Sq, nullptr, 0, 0};
-  const TextCtl ctl = make_ctl(p, b, p.Sk);
+  const TextCtl ctl = make_ctl<LO>(p, b, p.Sk);
   constexpr bool text = TEXT;          // vision instantiation: no mask / reweight / dropout code at all
   const LaneOffs lo = make_offs(lane);
 
@@ -1090,7 +1095,7 @@ __global__ __launch_bounds__(NTH, 2) void attn_bwd_dkv_k(mart_attn_bwd_desc pb) 
             const int ql = t * 32 + mfma_row(r, hh);
             const int qi = qt * 64 + ql;
             float f = 1.f, sc = st[r] * p.scale;
-            if (text) { f = reweight(ctl, qi, kj); sc = sc * f + maskadd; }
+            if (text) { f = reweight<LO>(ctl, qi, kj); sc = sc * f + maskadd; }
             const float pr = (kvalid && qi < p.Sq) ? __builtin_amdgcn_exp2f(sc * LOG2E - sLse[ql]) : 0.f;
             float keep = 1.f;
             if (TEXT && ctl.p_drop > 0.f) {
@@ -1549,7 +1554,8 @@ __device__ __forceinline__ void split8(const f32x4& a, const f32x4& b, bf16x8& h
     hi[4 + e] = (bf16)b[e]; lo[4 + e] = (bf16)(b[e] - (float)hi[4 + e]);
   }
 }
-template <int NW>      // waves per workgroup: 4 (128 queries) or 8 (256 queries: the K / V of a head are fetched and split half as often)
+// LO: the ViLT reweight rows (rw_row_lo > 0, as make_ctl<true>); the LO = false instantiations are the kernels as they were
+template <int NW, bool LO = false>      // waves per workgroup: 4 (128 queries) or 8 (256 queries: the K / V of a head are fetched and split half as often)
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_split_fwd_k(mart_attn_f32_desc p) {
   __shared__ __attribute__((aligned(16))) char sm[4 * SP_IMG];
   char* sKh = sm; char* sKl = sm + SP_IMG; char* sVh = sm + 2 * SP_IMG; char* sVl = sm + 3 * SP_IMG;
@@ -1578,7 +1584,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_split_fwd_k(mar
   if (p.sep) {
     sp = (int)p.sep[b * p.sep_stride];
     const float w0 = fminf(fmaxf(*p.w0, 0.f), 0.5f), w1 = fminf(fmaxf(*p.w1, 0.5f), 1.f);
-    rw = (p.rw_skip_row0 && qi == 0) ? 1.f : (qi < sp ? w0 : w1);
+    if (LO) {
+      const int lo_row = p.rw_row_lo > (p.rw_skip_row0 ? 1 : 0) ? p.rw_row_lo : (p.rw_skip_row0 ? 1 : 0);
+      rw = qi >= sp ? w1 : (qi < lo_row ? 1.f : w0);
+    } else {
+      rw = (p.rw_skip_row0 && qi == 0) ? 1.f : (qi < sp ? w0 : w1);
+    }
   }
   // staging: thread -> key row, NC 16-byte bf16 chunks (8 dims each) of K and of V: f32 rows kept in registers one tile ahead
   constexpr int NC = 8 / NW;                                           // chunks per thread: 64 rows x 8 chunks over 64 * NW threads
@@ -1714,6 +1725,7 @@ int check_fwd(const mart_attn_fwd_desc* d) {
   MART_CHECK((d->w0 == nullptr) == (d->w1 == nullptr), "attn: w0/w1 must come together");
   MART_CHECK(!d->sep || (d->w0 && d->Lp == 0), "attn: reweight needs w0/w1 and no prefix");
   MART_CHECK(!d->attn_mask || d->Lp == 0, "attn: mask with prefix unsupported");
+  MART_CHECK(d->rw_row_lo >= 0 && (d->rw_row_lo == 0 || d->sep), "attn: rw_row_lo needs the reweight (sep)");
   MART_CHECK(d->p_drop >= 0.f && d->p_drop < 1.f, "attn: bad dropout p");
   MART_CHECK(d->p_drop == 0.f || (long long)d->B * d->nh * d->Sq * (d->Lp + d->Sk) < (1LL << 32), "attn: dropout indices are 32-bit (B nh Sq Sk < 2^32)");
   return 0;
@@ -2020,11 +2032,12 @@ MartAttrOnce g_attr_once;
 int set_attrs() {
   bool* g_attr_set = g_attr_once.slot();
   if (*g_attr_set) return 0;
-  const void* ks[8] = {(const void*)attn_fwd_k<false, 1>, (const void*)attn_fwd_k<false, 2>, (const void*)attn_fwd_k<true, 1>,
-                       (const void*)attn_bwd_dq_k<false, 1>, (const void*)attn_bwd_dq_k<false, 2>, (const void*)attn_bwd_dq_k<true, 1>, (const void*)attn_bwd_dkv_k<false>,
-                       (const void*)attn_bwd_dkv_k<true>};
+  const void* ks[11] = {(const void*)attn_fwd_k<false, 1>, (const void*)attn_fwd_k<false, 2>, (const void*)attn_fwd_k<true, 1>,
+                        (const void*)attn_bwd_dq_k<false, 1>, (const void*)attn_bwd_dq_k<false, 2>, (const void*)attn_bwd_dq_k<true, 1>, (const void*)attn_bwd_dkv_k<false>,
+                        (const void*)attn_bwd_dkv_k<true>, (const void*)attn_fwd_k<true, 1, false, true>, (const void*)attn_bwd_dq_k<true, 1, true>,
+                        (const void*)attn_bwd_dkv_k<true, true>};
   bool ok = true;
-  for (int i = 0; i < 8; ++i) ok = ok && hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
+  for (int i = 0; i < 11; ++i) ok = ok && hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) == hipSuccess;
   ok = ok && hipFuncSetAttribute((const void*)attn_bwd_fused_k, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS) == hipSuccess;
 #ifdef MART_EXPERIMENTS
   ok = ok && hipFuncSetAttribute((const void*)attn_fwd_k<false, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 2 * TILE_BYTES) == hipSuccess;
@@ -2041,6 +2054,12 @@ int set_attrs() {
 // internal launcher for csrc/precise.hip (mart_attn_fwd_f32 routes its unmasked head-dim-64 calls of evaluation passes here)
 int mart_attn_split_launch(const mart_attn_f32_desc* d, void* stream) {
   static const int nw = getenv("MART_ATTN_SPLIT_WAVES") ? atoi(getenv("MART_ATTN_SPLIT_WAVES")) : 8;   // 0.858 vs 0.910 ms at the bench shape
+  if (d->rw_row_lo > 0) {
+    if (nw == 8 && d->Sq > 128) hipLaunchKernelGGL((attn_split_fwd_k<8, true>), dim3((d->Sq + 255) / 256, d->nh, d->B), dim3(512), 0, (hipStream_t)stream, *d);
+    else hipLaunchKernelGGL((attn_split_fwd_k<4, true>), dim3((d->Sq + 127) / 128, d->nh, d->B), dim3(256), 0, (hipStream_t)stream, *d);
+    MART_LAUNCH_CHECK();
+    return 0;
+  }
   if (nw == 8 && d->Sq > 128) hipLaunchKernelGGL(attn_split_fwd_k<8>, dim3((d->Sq + 255) / 256, d->nh, d->B), dim3(512), 0, (hipStream_t)stream, *d);
   else hipLaunchKernelGGL(attn_split_fwd_k<4>, dim3((d->Sq + 127) / 128, d->nh, d->B), dim3(256), 0, (hipStream_t)stream, *d);
   MART_LAUNCH_CHECK();
@@ -2067,7 +2086,8 @@ extern "C" int mart_attn_fwd(const mart_attn_fwd_desc* d, void* stream) {
     return 0;
   }
 #endif
-  if (text) hipLaunchKernelGGL((attn_fwd_k<true, 1>), dim3((d->Sq + 127) / 128, d->nh, d->B), dim3(NTH), LDS_BYTES, (hipStream_t)stream, *d);
+  if (text && d->rw_row_lo > 0) hipLaunchKernelGGL((attn_fwd_k<true, 1, false, true>), dim3((d->Sq + 127) / 128, d->nh, d->B), dim3(NTH), LDS_BYTES, (hipStream_t)stream, *d);
+  else if (text) hipLaunchKernelGGL((attn_fwd_k<true, 1>), dim3((d->Sq + 127) / 128, d->nh, d->B), dim3(NTH), LDS_BYTES, (hipStream_t)stream, *d);
   else if (tpw == 2 && d->Sq > 128) hipLaunchKernelGGL((attn_fwd_k<false, 2>), dim3((d->Sq + 255) / 256, d->nh, d->B), dim3(NTH), LDS_BYTES, (hipStream_t)stream, *d);
   else hipLaunchKernelGGL((attn_fwd_k<false, 1>), dim3((d->Sq + 32 * FWD_NW - 1) / (32 * FWD_NW), d->nh, d->B), dim3(64 * FWD_NW), LDS_BYTES, (hipStream_t)stream, *d);
   MART_LAUNCH_CHECK();
@@ -2095,7 +2115,8 @@ extern "C" int mart_attn_bwd(const mart_attn_bwd_desc* d, void* stream) {
   const bool al16 = d->lddq % 8 == 0 && d->lddk % 8 == 0 && d->lddv % 8 == 0 && (((uintptr_t)d->dq | (uintptr_t)d->dk | (uintptr_t)d->dv) & 15) == 0;
   // the whole score matrix of a head in one workgroup: one pass.  Text shapes (L = 64 / 96) and the short prefix-free vision shapes (CLIP-B/32
   // geometry: 100 tokens) alike -- every text option of the kernel is off when its operand is null
-  if (text_fused && al16 && f.Lp == 0 && f.Sq <= 128 && f.Sk <= 128) {
+  const bool lo = f.rw_row_lo > 0;                         // ViLT reweight rows: the two-pass kernels' LO instantiations
+  if (text_fused && al16 && !lo && f.Lp == 0 && f.Sq <= 128 && f.Sk <= 128) {
     const int mx = f.Sq > f.Sk ? f.Sq : f.Sk;                                             // 2 waves (64 x 64), 3 (96 x 96) or 4 (128 x 128)
     const bool drop = f.p_drop > 0.f;
     if (mx > 96) { if (drop) hipLaunchKernelGGL((attn_bwd_text64_k<true, 4>), dim3(f.nh, f.B), dim3(256), 0, st, *d); else hipLaunchKernelGGL((attn_bwd_text64_k<false, 4>), dim3(f.nh, f.B), dim3(256), 0, st, *d); }
@@ -2108,7 +2129,8 @@ extern "C" int mart_attn_bwd(const mart_attn_bwd_desc* d, void* stream) {
     }
     return 0;
   }
-  if (text) hipLaunchKernelGGL((attn_bwd_dq_k<true, 1>), dim3((f.Sq + 127) / 128, f.nh, f.B), dim3(NTH), LDS_BYTES, st, *d);
+  if (text && lo) hipLaunchKernelGGL((attn_bwd_dq_k<true, 1, true>), dim3((f.Sq + 127) / 128, f.nh, f.B), dim3(NTH), LDS_BYTES, st, *d);
+  else if (text) hipLaunchKernelGGL((attn_bwd_dq_k<true, 1>), dim3((f.Sq + 127) / 128, f.nh, f.B), dim3(NTH), LDS_BYTES, st, *d);
   else if (tpw == 2 && f.Sq > 128) hipLaunchKernelGGL((attn_bwd_dq_k<false, 2>), dim3((f.Sq + 255) / 256, f.nh, f.B), dim3(NTH), LDS_BYTES, st, *d);
   else hipLaunchKernelGGL((attn_bwd_dq_k<false, 1>), dim3((f.Sq + 127) / 128, f.nh, f.B), dim3(NTH), LDS_BYTES, st, *d);
   MART_LAUNCH_CHECK();
@@ -2117,7 +2139,8 @@ extern "C" int mart_attn_bwd(const mart_attn_bwd_desc* d, void* stream) {
     hipLaunchKernelGGL(attn_dw_reduce_k, dim3(1), dim3(1024), 0, st, d->dw_ws, n, f.w0, f.w1, d->dw);
     MART_LAUNCH_CHECK();
   }
-  if (text) hipLaunchKernelGGL(attn_bwd_dkv_k<true>, dim3((f.Lp + f.Sk + 127) / 128, f.nh, f.B), dim3(NTH), LDS_BYTES, st, *d);
+  if (text && lo) hipLaunchKernelGGL((attn_bwd_dkv_k<true, true>), dim3((f.Lp + f.Sk + 127) / 128, f.nh, f.B), dim3(NTH), LDS_BYTES, st, *d);
+  else if (text) hipLaunchKernelGGL(attn_bwd_dkv_k<true>, dim3((f.Lp + f.Sk + 127) / 128, f.nh, f.B), dim3(NTH), LDS_BYTES, st, *d);
   else hipLaunchKernelGGL(attn_bwd_dkv_k<false>, dim3((f.Lp + f.Sk + 127) / 128, f.nh, f.B), dim3(NTH), LDS_BYTES, st, *d);
   MART_LAUNCH_CHECK();
   return 0;

@@ -218,6 +218,7 @@ __global__ __launch_bounds__(256) void attn_f32_k(mart_attn_f32_desc p) {
 //   the probabilities never leave their registers.
 // Text options exactly as attn_f32_k (scale, adaptive reweight incl. the FLAVA row-0 variant, additive key mask), vision options: the [prefix | own] key set.
 constexpr int AM_WAVES = 4, AM_KT = 32, AM_LD = 65;
+template <bool LO = false>              // LO: the ViLT reweight rows (rw_row_lo > 0); LO = false is the kernel as it was
 __global__ __launch_bounds__(64 * AM_WAVES) void attn_f32_mfma_k(mart_attn_f32_desc p) {
   __shared__ float Ks[AM_KT * AM_LD], Vs[AM_KT * AM_LD];
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hf = lane >> 5;
@@ -238,7 +239,11 @@ __global__ __launch_bounds__(64 * AM_WAVES) void attn_f32_mfma_k(mart_attn_f32_d
     w0 = fminf(fmaxf(*p.w0, 0.f), 0.5f);
     w1 = fminf(fmaxf(*p.w1, 0.5f), 1.f);
   }
-  const float rw = (p.sep && !(p.rw_skip_row0 && qi == 0)) ? (qi < sp ? w0 : w1) : 1.f;     // factor of this query's scores at keys >= sp
+  float rw = (p.sep && !(p.rw_skip_row0 && qi == 0)) ? (qi < sp ? w0 : w1) : 1.f;     // factor of this query's scores at keys >= sp
+  if (LO) {
+    const int lo_row = p.rw_row_lo > (p.rw_skip_row0 ? 1 : 0) ? p.rw_row_lo : (p.rw_skip_row0 ? 1 : 0);
+    rw = qi >= sp ? w1 : (qi < lo_row ? 1.f : w0);
+  }
   f32x16 ot[2];
 #pragma unroll
   for (int r = 0; r < 16; ++r) { ot[0][r] = 0.f; ot[1][r] = 0.f; }
@@ -754,6 +759,7 @@ extern "C" int mart_attn_fwd_f32(const mart_attn_f32_desc* d, void* stream) {
   MART_CHECK(d->ldq % 4 == 0 && d->ldk % 4 == 0 && d->ldv % 4 == 0 && (d->Lp == 0 || (d->pk && d->pv && d->ldp % 4 == 0)), "attn_f32: bad strides / prefix");
   MART_CHECK((d->w0 == nullptr) == (d->w1 == nullptr) && (!d->sep || (d->w0 && d->Lp == 0)), "attn_f32: reweight needs w0/w1 and no prefix");
   MART_CHECK(!d->attn_mask || d->Lp == 0, "attn_f32: mask with prefix unsupported");
+  MART_CHECK(d->rw_row_lo >= 0 && (d->rw_row_lo == 0 || d->sep), "attn_f32: rw_row_lo needs the reweight (sep)");
   static const int scalar = getenv("MART_ATTN_F32_SCALAR") ? atoi(getenv("MART_ATTN_F32_SCALAR")) : 0;   // 1: the FMA-loop kernel (A/B, tests)
   static const int split_ok = getenv("MART_ATTN_F32_SPLIT") ? atoi(getenv("MART_ATTN_F32_SPLIT")) : 1;   // 0: exact f32 for evaluation passes too
   if (d->fast && split_ok && !scalar && d->D == 64 && d->ldctx % 4 == 0 && d->ldctx3 % 4 == 0 &&
@@ -763,7 +769,10 @@ extern "C" int mart_attn_fwd_f32(const mart_attn_f32_desc* d, void* stream) {
   MART_CHECK(!d->ctx_split3, "attn_f32: ctx_split3 is an output of the fast path only");
   if (d->D == 64 && !scalar && d->ldctx % 4 == 0 && ((uintptr_t)d->ctx & 15) == 0 && ((uintptr_t)d->k & 15) == 0 && ((uintptr_t)d->v & 15) == 0 &&
       (!d->pk || (((uintptr_t)d->pk & 15) == 0 && ((uintptr_t)d->pv & 15) == 0))) {
-    hipLaunchKernelGGL(attn_f32_mfma_k, dim3((d->Sq + 32 * AM_WAVES - 1) / (32 * AM_WAVES), d->nh, d->B), dim3(64 * AM_WAVES), 0, (hipStream_t)stream, *d);
+    if (d->rw_row_lo > 0)
+      hipLaunchKernelGGL(attn_f32_mfma_k<true>, dim3((d->Sq + 32 * AM_WAVES - 1) / (32 * AM_WAVES), d->nh, d->B), dim3(64 * AM_WAVES), 0, (hipStream_t)stream, *d);
+    else
+      hipLaunchKernelGGL(attn_f32_mfma_k<false>, dim3((d->Sq + 32 * AM_WAVES - 1) / (32 * AM_WAVES), d->nh, d->B), dim3(64 * AM_WAVES), 0, (hipStream_t)stream, *d);
     MART_LAUNCH_CHECK();
     return 0;
   }
@@ -785,6 +794,7 @@ extern "C" int mart_attn_fwd_f32(const mart_attn_f32_desc* d, void* stream) {
     MART_LAUNCH_CHECK();
     return 0;
   }
+  MART_CHECK(d->rw_row_lo == 0, "attn_f32: rw_row_lo needs D = 64 and 16-byte aligned operands (no scalar kernel)");
   if (d->D == 64) return launch_attn<64>(d, (hipStream_t)stream);
   if (d->D == 768) return launch_attn<768>(d, (hipStream_t)stream);
   mart_set_error("attn_f32: head dim must be 64 (multi-head attention) or 768 (fusion)");
@@ -823,6 +833,7 @@ extern "C" int mart_attn_bwd_f32(const mart_attn_bwd_f32_desc* d, void* stream) 
   MART_CHECK(d->f.B > 0 && d->f.nh > 0 && d->f.Sq > 0 && d->f.Sk > 0 && d->f.Lp >= 0, "attn_bwd_f32: bad shape");
   MART_CHECK(d->f.ldq % 4 == 0 && d->f.ldk % 4 == 0 && d->f.ldv % 4 == 0 && (d->f.Lp == 0 || (d->f.pk && d->f.pv && d->dpk && d->dpv && d->f.ldp % 4 == 0)), "attn_bwd_f32: bad strides / prefix");
   MART_CHECK((d->f.w0 == nullptr) == (d->f.w1 == nullptr) && (!d->f.sep || (d->f.w0 && d->f.Lp == 0)), "attn_bwd_f32: reweight needs w0/w1 and no prefix");
+  MART_CHECK(d->f.rw_row_lo == 0, "attn_bwd_f32: rw_row_lo is not supported (ViLT has no fp32 training path)");
   if (d->f.D == 64) return launch_attn_bwd<64>(d, (hipStream_t)stream);
   if (d->f.D == 768) return launch_attn_bwd<768>(d, (hipStream_t)stream);
   mart_set_error("attn_bwd_f32: head dim must be 64 or 768");

@@ -132,11 +132,12 @@ class KGC(BaseDataModule):
         with open(self.processor.entity_path, "r") as f:
             self.entities = [line.strip().split("\t")[0] for line in f.readlines()]
         if visual_features is None:
-            if a.model_class in ("VisualBertKGC", "VilBertKGC", "ViltKGC"):
-                raise NotImplementedError(f"{a.model_class} is outside the MKGformer/FLAVA hot path (SURVEY 8: out of scope)")
-            path = os.path.join(a.data_dir, "entity_image_features.CLIP-VIT-16-32.pth")
+            if a.model_class in ("VisualBertKGC", "VilBertKGC"):
+                raise NotImplementedError(f"{a.model_class} needs Faster R-CNN region features: outside the HIP path (SURVEY 8: out of scope)")
+            vilt = a.model_class == "ViltKGC"          # MarT data_module.py: ViLT reads its own 384-pixel table
+            path = os.path.join(a.data_dir, "entity_image_features_vilt.pth" if vilt else "entity_image_features.CLIP-VIT-16-32.pth")
             if not os.path.exists(path):
-                raise FileNotFoundError(f"{path} not found: pass visual_features=[N,3,224,224] or provide the file")
+                raise FileNotFoundError(f"{path} not found: pass visual_features=[N,3,{384 if vilt else 224},{384 if vilt else 224}] or provide the file")
             visual_features = torch.load(path)
         self.visual_features = visual_features
         self.image_table = DeviceImageTable(self.entities)

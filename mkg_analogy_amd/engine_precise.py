@@ -723,3 +723,59 @@ class PreciseFlavaTrain(PreciseFlavaForward):
 
     def score_train(self, trans: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, word_name: str, bias_name: str) -> torch.Tensor:
         return _PreciseScoreFn.apply(trans, rows, ids, self, word_name, bias_name)
+
+
+class PreciseViltForward(_PreciseBase):
+    """fp32-accurate twin of ``vilt_engine.ViltEngine.forward`` (MarT/models/modeling_vilt.py:760-869, :914-968) for evaluation passes: the joint
+    embedding (csrc/vilt.hip, f32 patch projection on split operands), 12 blocks of ``PreciseFlavaForward._block`` with the ViLT reweight rows
+    (``rw_row_lo``), final layernorm, MLM head transform on the text rows."""
+
+    _block = PreciseFlavaForward._block
+
+    def __init__(self, store: FlatStore, config):
+        self._init_base(store)
+        self.cfg = config
+        self.H, self.nh, self.I = config.hidden_size, config.num_attention_heads, config.intermediate_size
+        assert self.H // self.nh == 64
+        self.nl = config.num_hidden_layers
+        self.eps = float(config.layer_norm_eps)
+        self.n_tpos = int(config.max_position_embeddings)
+
+    @torch.no_grad()
+    def forward(self, input_ids, attention_mask, token_type_ids, pixel_values, sep_idx, patch_order, image_table=None, image_index=None):
+        st, H = self.st, self.H
+        dev = input_ids.device
+        B, L = input_ids.shape
+        S_img, p = self.cfg.image_size, self.cfg.patch_size
+        P = (S_img // p) ** 2
+        ni = 2 * (1 + P)
+        S = L + ni
+        Kp = 3 * p * p
+        patches = _e((B * 2 * P, Kp), F32, dev)
+        if image_index is not None:
+            ops.patchify_f32(image_table, image_index.contiguous().view(-1), patches, B, S_img, p)
+        else:
+            ops.patchify_f32(pixel_values.contiguous(), None, patches, B, S_img, p)
+        e, t = "vilt.embeddings.", "vilt.embeddings.text_embeddings."
+        pe = self.lin(patches, [e + "patch_embeddings.projection.weight"], [e + "patch_embeddings.projection.bias"], H)
+        del patches
+        x = _e((B * S, H), F32, dev)
+        ops.vilt_embed_fwd(ids=input_ids, tt=token_type_ids, word=st.m(t + "word_embeddings.weight"), tpos=st.m(t + "position_embeddings.weight"),
+                           ttype=st.m(t + "token_type_embeddings.weight"), gamma=st.m(t + "LayerNorm.weight"), beta=st.m(t + "LayerNorm.bias"),
+                           eps=self.eps, n_tpos=self.n_tpos, patch_f32=pe, cls=st.m(e + "cls_token"), ipos=st.m(e + "position_embeddings"),
+                           modality=st.m(e + "token_type_embeddings.weight"), perm=patch_order.to(device=dev, dtype=torch.int32).contiguous(),
+                           B=B, L=L, P=P, H=H, x=x, s_text=_e((B * L, H), F32, dev), mean=_e((B * L,), F32, dev), rstd=_e((B * L,), F32, dev))
+        from .vilt_engine import vilt_mask_and_sep
+        mask, sep = vilt_mask_and_sep(attention_mask, sep_idx, ni)
+        for l in range(self.nl):
+            pfx = f"vilt.encoder.layer.{l}."
+            a = pfx + "attention.attention."
+            x = self._block(pfx, x, B, S, attn_mask=mask, sep=sep, sep_stride=1, w0=st.m(a + "adaptive_weight.0"), w1=st.m(a + "adaptive_weight.1"),
+                            rw_row_lo=ni + 1)
+        xl = self._ln(x, "vilt.layernorm.weight", "vilt.layernorm.bias", self.eps)
+        rows = (torch.arange(B, device=dev, dtype=torch.int32)[:, None] * S + torch.arange(L, device=dev, dtype=torch.int32)[None]).reshape(-1).contiguous()
+        y = _e((B * L, H), F32, dev)
+        ops.gemm_nt(ops.split_bf16x3_rows(xl, rows, 0, terms=self.terms), self.w3(["mlm_score.transform.dense.weight"]), y,
+                    bias=st.m("mlm_score.transform.dense.bias"), act=ops.ACT_GELU)
+        trans = self._ln(y, "mlm_score.transform.LayerNorm.weight", "mlm_score.transform.LayerNorm.bias", self.eps)
+        return trans.view(B, L, H)

@@ -1,6 +1,7 @@
-from .model import FlavaKGC, MKGformerKGC
+from .model import FlavaKGC, MKGformerKGC, ViltKGC
 from .modeling_unimo import UnimoForMaskedLM
 from .modeling_flava import FlavaForMaskedLM, flava_config
+from .modeling_vilt import ViltForMaskedLM, draw_patch_order, vilt_config
 from .configs import TextConfig, VisionConfig
 
-__all__ = ["MKGformerKGC", "FlavaKGC", "UnimoForMaskedLM", "FlavaForMaskedLM", "flava_config", "TextConfig", "VisionConfig"]
+__all__ = ["MKGformerKGC", "FlavaKGC", "ViltKGC", "ViltForMaskedLM", "vilt_config", "draw_patch_order", "UnimoForMaskedLM", "FlavaForMaskedLM", "flava_config", "TextConfig", "VisionConfig"]

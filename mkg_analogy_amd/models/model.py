@@ -16,3 +16,12 @@ class FlavaKGC(__import__("mkg_analogy_amd.models.modeling_flava", fromlist=["Fl
     def add_to_argparse(parser):
         parser.add_argument("--pretrain", type=int, default=0, help="")
         return parser
+
+
+class ViltKGC(__import__("mkg_analogy_amd.models.modeling_vilt", fromlist=["ViltForMaskedLM"]).ViltForMaskedLM):
+    """MarT/models/model.py ViltKGC (fine-tune only: the reference cannot run the MarKG pre-train step with ViLT)."""
+
+    @staticmethod
+    def add_to_argparse(parser):
+        parser.add_argument("--pretrain", type=int, default=0, help="")
+        return parser

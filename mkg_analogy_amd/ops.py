@@ -203,7 +203,7 @@ def text_embed_scatter(ds, ids, tt, dword, dpos, dtype, B, Lq, H):
 
 
 def _attn_desc(d, *, q, k, v, ctx, lse, B, nh, Sq, Sk, scale, pk=None, pv=None, Lp=0, attn_mask=None, sep=None,
-               sep_stride=0, w0=None, w1=None, p_drop=0.0, seed=0, rw_skip_row0=False, ctx_f16=None):
+               sep_stride=0, w0=None, w1=None, p_drop=0.0, seed=0, rw_skip_row0=False, ctx_f16=None, rw_row_lo=0):
     d.q, d.k, d.v = _p(q), _p(k), _p(v)
     d.ctx_f16 = _p(ctx_f16)
     assert ctx_f16 is None or (_rows2d(ctx_f16) == _rows2d(ctx) and ctx_f16.dtype == F16)
@@ -214,6 +214,7 @@ def _attn_desc(d, *, q, k, v, ctx, lse, B, nh, Sq, Sk, scale, pk=None, pv=None, 
     d.p_drop, d.seed = p_drop, seed
     d.ctx, d.ldctx, d.lse = _p(ctx), _rows2d(ctx), _p(lse)
     d.rw_skip_row0 = int(rw_skip_row0)
+    d.rw_row_lo = int(rw_row_lo)
 
 
 def attn_fwd(**kw):
@@ -268,7 +269,7 @@ def vision_assemble_f32(patch, cls, pos, s, B, P, H, tail_shift=0):
 
 
 def attn_fwd_f32(*, q, k, v, ctx, B, nh, D, Sq, Sk, scale, pk=None, pv=None, Lp=0, attn_mask=None, sep=None, sep_stride=0,
-                 w0=None, w1=None, rw_skip_row0=False, fast=False, ctx_split3=None):
+                 w0=None, w1=None, rw_skip_row0=False, fast=False, ctx_split3=None, rw_row_lo=0):
     """``fast`` (evaluation passes): unmasked head-dim-64 calls may run on two-term bf16 operand splits (csrc/attention.hip attn_split_fwd_k);
     ``ctx_split3`` (fast path only, bf16 [rows, 3 * nh * D]): the context as the [hi | lo | hi] operand of the output projection (``ctx`` may be None)."""
     d = L.AttnF32()
@@ -279,6 +280,7 @@ def attn_fwd_f32(*, q, k, v, ctx, B, nh, D, Sq, Sk, scale, pk=None, pv=None, Lp=
     d.B, d.nh, d.D, d.Sq, d.Sk, d.scale = B, nh, D, Sq, Sk, scale
     d.attn_mask, d.sep, d.sep_stride, d.w0, d.w1, d.rw_skip_row0 = _p(attn_mask), _p(sep), sep_stride, _p(w0), _p(w1), int(rw_skip_row0)
     d.ctx, d.ldctx = _p(ctx), (_rows2d(ctx) if ctx is not None else 0)
+    d.rw_row_lo = int(rw_row_lo)
     L.check(L.lib().mart_attn_fwd_f32(C.byref(d), _stream()), "mart_attn_fwd_f32")
 
 
@@ -506,3 +508,32 @@ def block_table(src, dst, table, n):
 
 def transpose_table(src, dst, table, n):
     L.check(L.lib().mart_transpose_table(_p(src), _p(dst), _p(table), n, _stream()), "mart_transpose_table")
+
+
+# ---------------------------------------------------------------- ViLT joint embedding (csrc/vilt.hip)
+_LIBM = L                     # the binding module (the descriptor builder below takes a sequence length named L)
+
+
+def _vilt_desc(*, ids, tt, gamma, n_tpos, modality, perm, B, L, P, H, s_text, mean, rstd, word=None, tpos=None, ttype=None, beta=None, eps=0.0,
+               patch_f32=None, patch_bf16=None, cls=None, ipos=None, inv=None, x=None, dx=None, ds_text=None, dpatch=None, dgamma=None, dbeta=None,
+               dtpos=None, dttype=None, dcls=None, dipos=None, dmodality=None, ws=None):
+    assert ids.dtype == torch.int64 and tt.dtype == torch.int64 and perm.dtype == torch.int32 and tuple(perm.shape) == (2, B, P)
+    d = _LIBM.ViltEmbed()
+    d.ids, d.tt, d.word, d.tpos, d.ttype, d.gamma, d.beta, d.eps, d.n_tpos = _p(ids), _p(tt), _p(word), _p(tpos), _p(ttype), _p(gamma), _p(beta), eps, n_tpos
+    d.patch_f32, d.patch_bf16, d.cls, d.ipos, d.modality, d.perm, d.inv = _p(patch_f32), _p(patch_bf16), _p(cls), _p(ipos), _p(modality), _p(perm), _p(inv)
+    d.B, d.L, d.P, d.H = B, L, P, H
+    d.x, d.s_text, d.mean, d.rstd = _p(x), _p(s_text), _p(mean), _p(rstd)
+    d.dx, d.ds_text, d.dpatch = _p(dx), _p(ds_text), _p(dpatch)
+    d.dgamma, d.dbeta, d.dtpos, d.dttype, d.dcls, d.dipos, d.dmodality = _p(dgamma), _p(dbeta), _p(dtpos), _p(dttype), _p(dcls), _p(dipos), _p(dmodality)
+    d.ws, d.ws_bytes = _p(ws), (ws.numel() * 4 if ws is not None else 0)
+    return d
+
+
+def vilt_embed_fwd(**kw):
+    """x [B*S, H] f32 = the ViLT joint embedding (include/mart_hip.h mart_vilt_embed_desc); patch_f32 / patch_bf16 [B*2*P, H] in natural patch order."""
+    _LIBM.check(_LIBM.lib().mart_vilt_embed_fwd(C.byref(_vilt_desc(**kw)), _stream()), "mart_vilt_embed_fwd")
+
+
+def vilt_embed_bwd(**kw):
+    """ds_text, dpatch (un-permuted) written; every table gradient accumulated, in a fixed summation order."""
+    _LIBM.check(_LIBM.lib().mart_vilt_embed_bwd(C.byref(_vilt_desc(**kw)), _stream()), "mart_vilt_embed_bwd")
