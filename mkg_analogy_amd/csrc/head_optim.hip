@@ -171,6 +171,13 @@ __global__ void simloss_bwd_k(const float* __restrict__ tr, const int64_t* rel, 
 // step cover ~230 chunks each, and one workgroup per chunk left most CUs with a single 4-wave workgroup (2.6 TB/s); eight
 // parts per chunk put 7 workgroups on every CU.  Element-wise, so the split changes no result.
 constexpr int ADAMW_PART = 8192;
+// a * b rounded to fp32 on its own: the decayed weight, as torch's p.mul_(1 - lr * wd) leaves it.  Contracted into the subtraction of the Adam term
+// (one FMA, one rounding), weights near 1.0 -- where one ulp is 0.3 % of an update of ~lr -- land one ulp off the reference on every other step.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 __global__ __launch_bounds__(TPB) void adamw_k(mart_adamw_desc p) {
   const int parts = 65536 / ADAMW_PART;
   for (int wi = blockIdx.x; wi < p.n_chunks * parts; wi += gridDim.x) {
@@ -191,7 +198,7 @@ __global__ __launch_bounds__(TPB) void adamw_k(mart_adamw_desc p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float ge = g[e] * p.grad_scale;
-          w[e] *= decay;
+          w[e] = mul_rounded(w[e], decay);
           m[e] = p.beta1 * m[e] + (1.f - p.beta1) * ge;
           v[e] = p.beta2 * v[e] + (1.f - p.beta2) * ge * ge;
           w[e] -= step_size * m[e] / (sqrtf(v[e]) * inv_sqrt_bc2 + p.eps);
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(TPB) void adamw_k(mart_adamw_desc p) {
       } else {
         for (int e = 0; e < len - i; ++e) {
           const float ge = p.grad[o + e] * p.grad_scale;
-          float w = p.master[o + e] * decay;
+          float w = mul_rounded(p.master[o + e], decay);
           const float m = p.beta1 * p.m[o + e] + (1.f - p.beta1) * ge;
           const float v = p.beta2 * p.v[o + e] + (1.f - p.beta2) * ge * ge;
           w -= step_size * m / (sqrtf(v) * inv_sqrt_bc2 + p.eps);

@@ -19,7 +19,7 @@ from torch import nn
 from .. import functional as Fn
 from .. import ops
 from ..flava_engine import FlavaEngine, flava_f16_weight, flava_gemm_groups, flava_layout_order, FLAVA_DEAD
-from ..params import FlatStore
+from ..params import FlatStore, refresh_shadows_on_load
 from .modeling_unimo import MaskedLMOutput, _Container
 
 
@@ -173,6 +173,7 @@ class FlavaForMaskedLM(nn.Module):
         self._engine: Optional[FlavaEngine] = None
         self.image_table = None
         self.tie_weights()
+        refresh_shadows_on_load(self)
 
     # embedding surgery (same contract as the MKGformer class)
     def get_input_embeddings(self):
@@ -239,12 +240,6 @@ class FlavaForMaskedLM(nn.Module):
     def engine(self) -> FlavaEngine:
         self.finalize()
         return self._engine
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        if self._store is not None and self._store.owns(dict(self.named_parameters())):
-            self._store.refresh_shadows()
-        return r
 
     def sync_shadows(self):
         self.finalize().refresh_shadows()

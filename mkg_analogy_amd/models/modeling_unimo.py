@@ -21,7 +21,7 @@ from torch import nn
 from .. import functional as Fn
 from .. import ops
 from ..engine import UnimoEngine
-from ..params import FlatStore
+from ..params import FlatStore, refresh_shadows_on_load
 
 
 class _Container(nn.Module):
@@ -195,6 +195,7 @@ class UnimoForMaskedLM(nn.Module):
         self._precise_train = None
         self._mask_index: dict = {}                  # (device, B, nr) -> compact indices of slot 0 (row-subset passes)
         self.tie_weights()
+        refresh_shadows_on_load(self)
 
     # ------------------------------------------------------------------ embedding surgery (modeling_unimo.py:895-930)
     def get_input_embeddings(self):
@@ -266,12 +267,6 @@ class UnimoForMaskedLM(nn.Module):
     def engine(self) -> UnimoEngine:
         self.finalize()
         return self._engine
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        if self._store is not None and self._store.owns(self._named()):
-            self._store.refresh_shadows()
-        return r
 
     def set_precision(self, precision: str):
         """"bf16" (default: bf16 MFMA operands, fp32 accumulation / residual streams; training + eval) or "fp32"

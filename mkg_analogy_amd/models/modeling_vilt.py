@@ -17,7 +17,7 @@ from torch import nn
 
 from .. import functional as Fn
 from .. import ops
-from ..params import FlatStore
+from ..params import FlatStore, refresh_shadows_on_load
 from ..vilt_engine import VILT_DEAD, WORD, ViltEngine, vilt_f16_weight, vilt_gemm_groups, vilt_layout_order
 from .modeling_flava import FlavaLayer
 from .modeling_unimo import MaskedLMOutput, _Container
@@ -125,6 +125,7 @@ class ViltForMaskedLM(nn.Module):
         self._engine: Optional[ViltEngine] = None
         self.image_table = None
         self.tie_weights()
+        refresh_shadows_on_load(self)
 
     # embedding surgery (same contract as the MKGformer / FLAVA classes)
     def get_input_embeddings(self):
@@ -194,12 +195,6 @@ class ViltForMaskedLM(nn.Module):
     def engine(self) -> ViltEngine:
         self.finalize()
         return self._engine
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        r = super().load_state_dict(state_dict, strict=strict, **kw)
-        if self._store is not None and self._store.owns(dict(self.named_parameters())):
-            self._store.refresh_shadows()
-        return r
 
     def sync_shadows(self):
         self.finalize().refresh_shadows()

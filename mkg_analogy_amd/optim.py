@@ -7,7 +7,7 @@ import os
 import torch
 
 from . import ops
-from .params import NO_DECAY
+from .params import NO_DECAY, check_layout, layout_list
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -55,8 +55,8 @@ class FusedAdamW(torch.optim.Optimizer):
         writes gradients waits for it first (FlatStore.join_pending: the model's forward call joins before returning, and every
         backward kernel is enqueued later).  Default (``MART_ASYNC_STEP=0``): the plain in-order fill."""
         store = self.model.store
-        if getattr(store, "grad_clean", False):
-            return                                                       # zeroed by the last update (fused_zero_grad) and not written since
+        if store.grad_is_clean():
+            return                                                       # zeroed by the last update (fused_zero_grad) and not written since (by a kernel or through p.grad)
         if not (self.async_step and store.grad.is_cuda):
             store.zero_grad()
             return
@@ -125,7 +125,9 @@ class FusedAdamW(torch.optim.Optimizer):
         self._launch(store.n_chunks)
         self._streaming = False
         if self.fused_zero_grad:
-            store.grad_clean = True                                       # every chunk's gradients were zeroed by its update; nothing else is ever written
+            # every chunk's gradients were zeroed by its update; the ranges outside the chunk table (dead tensors) are never written by a kernel, so
+            # they still hold the zeros of the last fill -- and if anything else wrote them, through p.grad, grad_is_clean() sees the version move
+            store.mark_grad_clean()
         if self._stream is not None:
             torch.cuda.current_stream().wait_stream(self._stream)       # master + bf16 / fp16 shadows are final for the next forward pass
         if self.async_step and self._stream is not None and store.grad.is_cuda:
@@ -136,12 +138,22 @@ class FusedAdamW(torch.optim.Optimizer):
             store.refresh_transposed()
 
     def state_dict(self):
-        return {"m": self.m, "v": self.v, "steps": self.steps, "lr": self.param_groups[0]["lr"]}
+        """Flat ``m`` / ``v`` (one element per element of the master buffer) WITH the layout they belong to, the step count, and the state of the
+        schedule that drives ``lr`` (LinearWarmupSchedule attaches itself), so that a resume needs nothing else."""
+        sd = {"m": self.m, "v": self.v, "steps": self.steps, "lr": self.param_groups[0]["lr"], "layout": layout_list(self.model.store.slots)}
+        if getattr(self, "_schedule", None) is not None:
+            sd["scheduler"] = self._schedule.state_dict()
+        return sd
 
     def load_state_dict(self, sd):
+        check_layout(sd.get("layout"), self.model.store.slots)
+        if tuple(sd["m"].shape) != tuple(self.m.shape) or tuple(sd["v"].shape) != tuple(self.v.shape):
+            raise ValueError(f"optimizer state holds {tuple(sd['m'].shape)} moments, this model stores {tuple(self.m.shape)}")
         self.m.copy_(sd["m"]); self.v.copy_(sd["v"]); self.steps = int(sd["steps"])
         for g in self.param_groups:
             g["lr"] = sd["lr"]
+        if "scheduler" in sd and getattr(self, "_schedule", None) is not None:
+            self._schedule.load_state_dict(sd["scheduler"])
 
 
 class TorchOptimizerOnStore:
@@ -193,6 +205,8 @@ class LinearWarmupSchedule:
         self.w, self.T = num_warmup_steps, num_training_steps
         self.base_lrs = [g["lr"] for g in optimizer.param_groups]
         self.last_epoch = last_epoch
+        if hasattr(optimizer, "fused_zero_grad"):
+            optimizer._schedule = self                                 # FusedAdamW.state_dict carries the schedule's step
         self.step()                                                    # like torch's LambdaLR: lr(0) applied at construction
 
     def lr_lambda(self, t: int) -> float:

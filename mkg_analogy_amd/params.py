@@ -66,7 +66,43 @@ def layout_order(n_layers: int) -> List[str]:
     return o
 
 
-DEAD = ("unimo.vision_post_layernorm.", "unimo.text_pooler.")
+# never receive a gradient in the reference (grad None => torch.optim skips them: no update, no weight decay): the unused post layernorm and pooler,
+# and ``fusion_dense`` of the text layers below the first fusion layer (modeling_unimo.py:616,627: the visual stream reaches layers >= 8 only)
+DEAD = ("unimo.vision_post_layernorm.", "unimo.text_pooler.") + tuple(f"unimo.encoder.text_layer.{l}.intermediate.fusion_dense." for l in range(8))
+
+
+def layout_list(slots: Dict[str, "Slot"]) -> List[List]:
+    """[name, offset, numel] of every slot in layout order: what a flat optimizer state (one m / v element per master element) belongs to."""
+    return [[s.name, int(s.offset), int(s.numel)] for s in slots.values()]
+
+
+def check_layout(saved, slots: Dict[str, "Slot"]) -> None:
+    """Raise unless ``saved`` (``layout_list`` of the store a flat state was written from) is this store's layout: the same bytes would otherwise
+    load without any error onto other parameters (the layout order has changed between versions, and differs between backbones)."""
+    if saved is None:
+        raise ValueError("optimizer state carries no parameter layout: a flat m / v written without one cannot be matched to parameters")
+    mine = layout_list(slots)
+    saved = [[str(n), int(o), int(k)] for n, o, k in saved]
+    if saved == mine:
+        return
+    if len(saved) != len(mine):
+        raise ValueError(f"optimizer state was written for {len(saved)} tensors, this model stores {len(mine)}")
+    i = next(i for i, (a, b) in enumerate(zip(saved, mine)) if a != b)
+    raise ValueError(f"optimizer state was written for another parameter layout: entry {i} is {saved[i]}, this model has {mine[i]}")
+
+
+def _refresh_after_load(module, incompatible_keys) -> None:
+    st = getattr(module, "_store", None)
+    if st is not None and st.owns(dict(module.named_parameters())):
+        st.refresh_shadows()
+
+
+def refresh_shadows_on_load(model: torch.nn.Module) -> None:
+    """The parameters are views of the fp32 master buffer, so ``load_state_dict`` writes the masters; the bf16 / fp16 / W^T copies that every kernel
+    reads must follow.  A post-hook (not an override of ``load_state_dict``): torch runs it for a load through ANY ancestor -- the reference reloads
+    its best checkpoint through the lit model (main.py:134,159), which calls ``_load_from_state_dict`` of the submodules, never their
+    ``load_state_dict`` -- and exactly once per load."""
+    model.register_load_state_dict_post_hook(_refresh_after_load)
 
 
 def text_f16_weight(name: str) -> bool:
@@ -154,7 +190,7 @@ class FlatStore:
         # AdamW chunk table: (start, len, decay_flag); dead tensors are excluded (grad None in the reference => untouched)
         self.order = order
         self.version = 0                                           # bumped whenever the master weights change (derived operand caches)
-        self.grad_clean = True                                     # the gradient buffer is all-zero (FusedAdamW.fused_zero_grad / zero_grad)
+        self.mark_grad_clean()                                     # the gradient buffer is all-zero (FusedAdamW.fused_zero_grad / zero_grad)
         self.rebuild_chunks()
         self.refresh_shadows()
 
@@ -276,7 +312,16 @@ class FlatStore:
     def zero_grad(self) -> None:
         self.join_pending()
         self.grad.zero_()
+        self.mark_grad_clean()
+
+    def mark_grad_clean(self) -> None:
+        """The gradient buffer is all-zero now.  The claim holds until a kernel is handed a gradient destination (g() / fused() / touch_grad() clear the
+        flag) or torch writes through ``grad`` or any ``p.grad`` view of it: those share one version counter, recorded here."""
         self.grad_clean = True
+        self._clean_version = self.grad._version
+
+    def grad_is_clean(self) -> bool:
+        return bool(self.grad_clean) and self.grad._version == getattr(self, "_clean_version", -1)
 
     def touch_grad(self) -> None:
         """For writers that go to ``store.grad`` / ``p.grad`` directly (g() and fused(.., grad) mark the buffer themselves): no longer all-zero."""

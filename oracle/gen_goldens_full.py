@@ -68,9 +68,11 @@ def grad_sample(g: torch.Tensor, n: int = 1024) -> np.ndarray:
     return f[::step][:n].numpy().copy()
 
 
-def build_reference(lit, unimo, patch, sd0, pretrain, cfg):
+def build_reference(lit, unimo, patch, sd0, pretrain, cfg, dropout=None):
     vc, tc0 = O.VisionCfg(patch_size=patch), O.TextCfg(vocab_size=BASE)
     hv, ht = hf_configs(vc, tc0)
+    if dropout is not None:                            # G11 (gen_goldens_traj.py): train mode made deterministic
+        ht.hidden_dropout_prob = ht.attention_probs_dropout_prob = float(dropout)
     torch.manual_seed(0)
     model = unimo.UnimoForMaskedLM(hv, ht)
     tok = FakeTokenizer(BASE + NE + NR)

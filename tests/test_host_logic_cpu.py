@@ -323,3 +323,30 @@ def test_scored_ids_uniqueness_check_is_per_tensor_object_not_per_address():
     rng._mart_unique = True                                   # LazyRows marks ranges: no check, no device sync
     Fn._require_unique(rng)
     assert len(Fn._UNIQUE_OK) <= 66
+
+
+def test_optimizer_state_layout_check():
+    """params.check_layout: a flat optimizer state (one m / v element per master element) is only accepted for the slot list it was written
+    from -- same names, offsets and sizes in the same order."""
+    from mkg_analogy_amd.params import Slot, check_layout, layout_list
+    slots = {n: Slot(n, (k,), o, k) for n, o, k in (("a.weight", 0, 300), ("a.bias", 512, 3), ("b.weight", 768, 256))}
+    saved = layout_list(slots)
+    assert saved == [["a.weight", 0, 300], ["a.bias", 512, 3], ["b.weight", 768, 256]]
+    check_layout(saved, slots)
+    check_layout([tuple(e) for e in saved], slots)                      # what a round trip through a file may turn the lists into
+    with pytest.raises(ValueError, match="another parameter layout: entry 0"):
+        check_layout([saved[2], saved[1], saved[0]], slots)             # two slots permuted
+    with pytest.raises(ValueError, match="another parameter layout: entry 1"):
+        check_layout([saved[0], ["a.bias", 256, 3], saved[2]], slots)   # the same names at other offsets
+    with pytest.raises(ValueError, match="2 tensors"):
+        check_layout(saved[:2], slots)
+    with pytest.raises(ValueError, match="no parameter layout"):
+        check_layout(None, slots)
+
+
+def test_dead_list_covers_every_tensor_without_gradient_in_the_reference(golden_dir):
+    """The 20 tensors whose gradient is None after a fine-tune step of the reference (golden G11) are exactly the ones the AdamW chunk table leaves
+    out: torch.optim skips them, so they get no update and NO weight decay."""
+    from mkg_analogy_amd.params import DEAD, layout_order
+    none = set(np.load(os.path.join(golden_dir, "g11_traj.npz"))["none_grad"].tolist())
+    assert {n for n in layout_order(12) if n.startswith(DEAD)} == none

@@ -177,7 +177,8 @@ def test_forward_backward_vs_oracle(patch, B, conditioned, L):
 
 def test_train_mode_step_and_optimizer():
     """Dropout on: loss finite and close to eval loss; 3 fused-AdamW steps reduce the loss on a fixed batch;
-    parameter update matches torch.optim.AdamW applied to the same gradients."""
+    parameter update matches torch.optim.AdamW applied to the same gradients.  (The closed form below uses the optimizer's own moments; the
+    trajectory against the reference's optimizer is held in tests/test_trajectory_gpu.py.)"""
     from mkg_analogy_amd import data_synth as D
     from mkg_analogy_amd.trainer import Trainer
     model, lit, cfg, vc = _product(32, seed=5)

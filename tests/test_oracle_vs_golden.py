@@ -336,6 +336,36 @@ def test_g7_conditioned_golden_and_its_bf16_weight_control():
     assert 8e-3 < float(np.abs(d).max()) < 1.3e-2 and 1.8e-3 < float(np.sqrt((d ** 2).mean())) < 2.6e-3   # the bf16 floor of this batch: 1.02e-2 / 2.17e-3
 
 
+def test_g11_trajectory_golden_first_losses_and_files(golden_dir):
+    """G11 (oracle/gen_goldens_traj.py): the reference's warm-up starts at lr = 0, so its first TWO losses are taken at the initial weights --
+    the oracle reproduces both (batches 0 and 1, dropout 0); the five files are present, below the size limit for a committed file, and the
+    controls start from the same first-step loss up to their perturbation."""
+    from mkg_analogy_amd import data_synth as D
+    torch.set_num_threads(max(1, min(16, (os.cpu_count() or 8))))
+    files = ["g11_traj.npz", "g11_traj_main.npz", "g11_traj_acc2.npz", "g11_traj_ctlbf.npz", "g11_traj_ctl32.npz"]
+    for f in files:
+        assert 0 < os.path.getsize(os.path.join(golden_dir, f)) < (1 << 20), f
+    g = dict(np.load(os.path.join(golden_dir, "g11_traj.npz"), allow_pickle=False))
+    assert g["lr"][0] == 0.0 and g["acc2::lr"][0] == 0.0 and len(g["none_grad"]) == 20
+    assert np.array_equal(g["loss"][:2], g["acc2::loss"][:2]) and np.array_equal(g["loss"][:2], g["ctl32::loss"][:2])
+    assert 0 < abs(g["ctlbf::loss"][0] - g["loss"][0]) < 5e-3
+    vc = O.VisionCfg(patch_size=int(g["patch"]))
+    sd = O.condition_weights(O.init_params(vc, O.TextCfg(vocab_size=D.BASE_VOCAB + D.N_ENT + D.N_REL), seed=int(g["weight_seed"])))
+    cfg = D.data_config(seed=1234)
+    sd = O.init_relation_word(sd, cfg["analogy_relation_ids"])
+    tc = O.TextCfg(vocab_size=D.VOCAB)
+    ids = torch.tensor(cfg["analogy_entity_ids"])
+    for i in (0, 1):
+        b = D.make_batch(int(g["B"]), int(g["L"]), seed=int(g["batch_seeds"][i]))
+        for k, v in b.items():
+            if k != "pixel_values":
+                assert np.array_equal(v.numpy(), g[f"in{i}::" + k]), (i, k)
+        with torch.no_grad():
+            _, trans = O.forward(sd, vc, tc, b["input_ids"], b["attention_mask"], b["token_type_ids"], b["pixel_values"], b["sep_idx"], train=False)
+            loss, _ = O.finetune_loss(sd, trans, b["input_ids"], b["label"], b["rel_idx"], b["q_head_idx"], b["a_head_idx"], ids, alpha=0.43)
+        assert abs(float(loss) - float(g["loss"][i])) < 2e-5, (i, float(loss), float(g["loss"][i]))
+
+
 def test_g9_flava_oracle_matches_reference_at_real_dimensions(golden_dir):
     """G9: flava_oracle against the UNMODIFIED reference FlavaForMaskedLM at real dimensions (768 wide, 12 + 12 + 6 layers, 393 image
     tokens, L = 64, V = 42007; B = 2): mask logits, trans rows, loss, gradient norms.  (G5 pins it at tiny dimensions.)"""
