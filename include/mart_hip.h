@@ -222,6 +222,34 @@ typedef struct {
 int mart_vilt_embed_fwd(const mart_vilt_embed_desc* d, void* stream);
 int mart_vilt_embed_bwd(const mart_vilt_embed_desc* d, void* stream);
 
+/* ---------------------------------------------------------------- VisualBERT joint embedding (modeling_visual_bert.py:105-200, csrc/visual_bert.hip)
+ * Joint stream x [B*S, H] f32, S = L + V, text first, then V region rows:
+ *   text t   : word[id] + type[tt] + pos[t]
+ *   visual j : proj[b*V + j] + vpos + vtype      (proj = the f32 output of the projection GEMM incl. its bias; vpos = visual_position_embeddings
+ *              row 0, vtype = visual_token_type_embeddings row 1: MarT passes neither an alignment nor visual type ids)
+ *   x = dropout(LayerNorm(row), p_drop): output element o = row * H + c is kept as mart_ln_fwd keeps element o for the same seed.
+ * Forward also writes the LayerNorm input s [B*S, H] and mean / rstd [B*S] for the backward pass, and optional 16-bit copies of x (the A operand of
+ * layer 0's Q/K/V GEMM).  Backward (deterministic, no float atomics): ds_text = d(LayerNorm input) of the text rows [B*L, H] (the word-row
+ * scatter's operand), dproj bf16 [B*V, H] (gemm_tn against the features), and dgamma, dbeta, dpos[:L], dtype[2], dvpos[H], dvtype[H] ACCUMULATED
+ * (+=).  ws: (B * V + 4 (L + V)) * H floats.  Any L, V >= 1; H % 256 == 0, H <= 1024. */
+typedef struct {
+  const int64_t* ids; const int64_t* tt;                            /* [B, L] */
+  const float* word; const float* pos; const float* type;           /* text tables */
+  const float* vpos; const float* vtype;                            /* [H] each: the one row of each visual table MarT reads */
+  const float* proj;                                                /* [B*V, H] f32 (forward) */
+  const float* gamma; const float* beta; float eps;
+  float p_drop; uint64_t seed;
+  int B, L, V, H;
+  float* x; void* x_bf16; void* x_f16;                              /* forward outputs [B*S, H]; the 16-bit copies are optional */
+  float* s; float* mean; float* rstd;                               /* LayerNorm input [B*S, H] and statistics [B*S]: written forward, read backward */
+  const float* dx;                                                  /* backward input [B*S, H] */
+  float* ds_text; void* dproj;
+  float* dgamma; float* dbeta; float* dpos; float* dtype; float* dvpos; float* dvtype;
+  float* ws; long long ws_bytes;
+} mart_vbert_embed_desc;
+int mart_vbert_embed_fwd(const mart_vbert_embed_desc* d, void* stream);
+int mart_vbert_embed_bwd(const mart_vbert_embed_desc* d, void* stream);
+
 /* ---------------------------------------------------------------- attention (head_dim 64)
  * Flash-style multi-head attention, K/V tiles staged in LDS, wave-level online softmax.
  *  vision: CLIPAttention.forward, modeling_unimo.py:212-272 -- no mask, keys = [text prefix (K,V) | own]

@@ -91,6 +91,13 @@ class ViltEmbed(C.Structure):
                 ("dcls", vp), ("dipos", vp), ("dmodality", vp), ("ws", vp), ("ws_bytes", i64)]
 
 
+class VbertEmbed(C.Structure):
+    _fields_ = [("ids", vp), ("tt", vp), ("word", vp), ("pos", vp), ("type", vp), ("vpos", vp), ("vtype", vp), ("proj", vp),
+                ("gamma", vp), ("beta", vp), ("eps", f32), ("p_drop", f32), ("seed", u64), ("B", i32), ("L", i32), ("V", i32), ("H", i32),
+                ("x", vp), ("x_bf16", vp), ("x_f16", vp), ("s", vp), ("mean", vp), ("rstd", vp), ("dx", vp), ("ds_text", vp), ("dproj", vp),
+                ("dgamma", vp), ("dbeta", vp), ("dpos", vp), ("dtype", vp), ("dvpos", vp), ("dvtype", vp), ("ws", vp), ("ws_bytes", i64)]
+
+
 class FusionFwd(C.Structure):
     _fields_ = [("q", vp), ("ldq", i32), ("v", vp), ("ldv", i32), ("out", vp), ("ldo", i32), ("probs", vp), ("ldp", i32),
                 ("B", i32), ("Lq", i32), ("Nv", i32), ("H", i32), ("out_f16", vp)]
@@ -177,6 +184,8 @@ _SIGS = {
     "mart_attn_fwd_f32": (i32, [vp, vp]),
     "mart_vilt_embed_fwd": (i32, [C.POINTER(ViltEmbed), vp]),
     "mart_vilt_embed_bwd": (i32, [C.POINTER(ViltEmbed), vp]),
+    "mart_vbert_embed_fwd": (i32, [C.POINTER(VbertEmbed), vp]),
+    "mart_vbert_embed_bwd": (i32, [C.POINTER(VbertEmbed), vp]),
 }
 
 EXPORTS = tuple(_SIGS)

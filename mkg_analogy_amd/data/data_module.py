@@ -78,6 +78,30 @@ class DataCollatorForSeq2Seq:
     num_labels: int = 0
     image_table: Optional[DeviceImageTable] = None        # entity -> row of the HBM-resident image table
     visual_features: Optional[torch.Tensor] = None         # CPU [N,3,H,W]: emit pixel_values like the reference
+    region_features: Optional[Dict[str, Any]] = None       # VisualBERT: entity -> Faster R-CNN region array [1, 36, 2048] or [36, 2048]
+
+    def _regions(self, head_ent, tail_ent):
+        """pixel_values [B, 72, 2048] f32 and visual_attention_mask [B, 72] float of the reference's dict branch (:121-159): both entities present:
+        (head, tail), all ones; otherwise entity = head if head is not None else tail: (entity or a zero block with a zero mask, zero block)."""
+        import numpy as np
+        tab = self.region_features
+        R, Fd = 36, 2048
+        get = lambda e: torch.from_numpy(np.asarray(tab[e])).squeeze().to(torch.float32)
+        pix, vm = [], []
+        for head, tail in zip(head_ent, tail_ent):
+            if head and tail:
+                p, m = [get(head), get(tail)], [torch.ones(R), torch.ones(R)]
+            else:
+                entity = head if head is not None else tail
+                if entity:
+                    p, m = [get(entity)], [torch.ones(R)]
+                else:
+                    p, m = [torch.zeros((R, Fd))], [torch.zeros(R)]
+                p.append(torch.zeros((R, Fd)))
+                m.append(torch.zeros(R))
+            pix.append(torch.cat(p))
+            vm.append(torch.cat(m))
+        return torch.stack(pix), torch.stack(vm)
 
     def __call__(self, features: Sequence[Dict[str, Any]], return_tensors=None) -> Dict[str, Any]:
         return_tensors = self.return_tensors if return_tensors is None else return_tensors
@@ -89,7 +113,9 @@ class DataCollatorForSeq2Seq:
                                    return_tensors=return_tensors)
         batch = dict(batch)
         head_ent, tail_ent = col.get("head_ent"), col.get("tail_ent")
-        if head_ent is not None and self.image_table is not None:
+        if head_ent is not None and self.region_features is not None:
+            batch["pixel_values"], batch["visual_attention_mask"] = self._regions(head_ent, tail_ent)
+        elif head_ent is not None and self.image_table is not None:
             slots = self.image_table.slots(head_ent, tail_ent)                       # [B,2] int32, -1 = zero image
             if self.visual_features is not None:
                 tab = self.visual_features
@@ -117,9 +143,10 @@ class DataCollatorForSeq2Seq:
 
 
 class KGC(BaseDataModule):
-    def __init__(self, args, model=None, tokenizer=None, visual_features: Optional[torch.Tensor] = None) -> None:
+    def __init__(self, args, model=None, tokenizer=None, visual_features: Optional[Union[torch.Tensor, Dict[str, Any]]] = None) -> None:
         """``tokenizer`` / ``visual_features`` may be injected (tests, synthetic runs); by default they are read from
-        ``args.model_name_or_path/vocab.txt`` and ``args.data_dir/entity_image_features.CLIP-VIT-16-32.pth`` (:207)."""
+        ``args.model_name_or_path/vocab.txt`` and ``args.data_dir/entity_image_features.CLIP-VIT-16-32.pth`` (:207).  ``VisualBertKGC`` takes
+        ``visual_features`` as a dict entity -> region array and has no default."""
         super().__init__(args)
         a = self.args
         self.tokenizer = tokenizer if tokenizer is not None else \
@@ -131,9 +158,18 @@ class KGC(BaseDataModule):
         self.tokenizer.add_special_tokens({"additional_special_tokens": entity_list})
         with open(self.processor.entity_path, "r") as f:
             self.entities = [line.strip().split("\t")[0] for line in f.readlines()]
+        if a.model_class == "VilBertKGC":
+            raise NotImplementedError("VilBertKGC (two-stream ViLBERT over Faster R-CNN regions) is outside the HIP path")
+        self.region_mode = a.model_class == "VisualBertKGC"
+        if self.region_mode:
+            # the module neither runs the detector nor unpickles a file on its own: the caller injects the dict (KGC.load_region_features reads
+            # the reference's analogy_entity2vec.pickle for those who have it)
+            if visual_features is None:
+                raise NotImplementedError("VisualBertKGC needs Faster R-CNN region features: pass visual_features={entity: array [36, 2048]} "
+                                          "(KGC.load_region_features(path) reads analogy_entity2vec.pickle)")
+            if not isinstance(visual_features, dict):
+                raise TypeError("VisualBertKGC: visual_features must be a dict entity -> array [1, 36, 2048] or [36, 2048]")
         if visual_features is None:
-            if a.model_class in ("VisualBertKGC", "VilBertKGC"):
-                raise NotImplementedError(f"{a.model_class} needs Faster R-CNN region features: outside the HIP path (SURVEY 8: out of scope)")
             vilt = a.model_class == "ViltKGC"          # MarT data_module.py: ViLT reads its own 384-pixel table
             path = os.path.join(a.data_dir, "entity_image_features_vilt.pth" if vilt else "entity_image_features.CLIP-VIT-16-32.pth")
             if not os.path.exists(path):
@@ -159,15 +195,29 @@ class KGC(BaseDataModule):
         return DataCollatorForSeq2Seq(self.tokenizer, model=model, label_pad_token_id=self.tokenizer.pad_token_id,
                                       pad_to_multiple_of=8 if a.precision == 16 else None, padding="longest",
                                       max_length=a.max_seq_length, num_labels=len(self.entities),
-                                      image_table=self.image_table,
-                                      visual_features=self.visual_features if self.emit_pixel_values else None)
+                                      image_table=None if self.region_mode else self.image_table,
+                                      visual_features=self.visual_features if self.emit_pixel_values and not self.region_mode else None,
+                                      region_features=self.visual_features if self.region_mode else None)
 
     def use_host_pixels(self, flag: bool = True) -> None:
         self.emit_pixel_values = flag
         self.sampler = self._make_sampler(self.sampler.model)
 
+    @staticmethod
+    def load_region_features(path: str) -> Dict[str, Any]:
+        """The reference's ``analogy_entity2vec.pickle`` (entity -> Faster R-CNN features [1, 36, 2048]) as the dict ``visual_features`` takes for
+        ``VisualBertKGC``.  Explicit on purpose: a pickle executes code when loaded, so only the caller who trusts the file opens it."""
+        import pickle
+        with open(path, "rb") as f:
+            table = pickle.load(f)
+        if not isinstance(table, dict):
+            raise TypeError(f"{path}: expected a dict entity -> region features, found {type(table).__name__}")
+        return table
+
     def attach(self, model) -> None:
         """Upload the image table once; batches then carry ``image_index`` only."""
+        if self.region_mode:
+            raise NotImplementedError("region features travel in every batch (pixel_values [B, 72, 2048]); the device table holds pixels only")
         model.set_image_table(self.visual_features)
 
     def _fresh_tokenizer(self):

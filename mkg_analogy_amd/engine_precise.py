@@ -779,3 +779,57 @@ class PreciseViltForward(_PreciseBase):
                     bias=st.m("mlm_score.transform.dense.bias"), act=ops.ACT_GELU)
         trans = self._ln(y, "mlm_score.transform.LayerNorm.weight", "mlm_score.transform.LayerNorm.bias", self.eps)
         return trans.view(B, L, H)
+
+
+class PreciseVisualBertForward(_PreciseBase):
+    """fp32-accurate twin of ``visual_bert_engine.VisualBertEngine.forward`` (MarT/models/modeling_visual_bert.py:854-911, :1664-1723) for
+    evaluation passes: the visual projection on split operands, the joint embedding (csrc/visual_bert.hip, dropout off), 12 post-LN blocks with
+    the VisualBERT reweight rows (``rw_row_lo``) and the joint, non-prefix key mask, MLM head transform on all S rows."""
+
+    def __init__(self, store: FlatStore, config):
+        self._init_base(store)
+        self.cfg = config
+        self.H, self.nh, self.I = config.hidden_size, config.num_attention_heads, config.intermediate_size
+        assert self.H // self.nh == 64
+        self.nl = config.num_hidden_layers
+        self.eps = float(config.layer_norm_eps)
+
+    def _block(self, p: str, x: torch.Tensor, B: int, S: int, **attn):
+        """VisualBertLayer.forward: LN(x + dense(Attn(x))); LN(a + dense(GELU(dense(a))))."""
+        H, I = self.H, self.I
+        a_ = p + "attention.self."
+        pre3 = self._pre()
+        qkv = self.lin(x, [a_ + f"{n}.weight" for n in ("query", "key", "value")], [a_ + f"{n}.bias" for n in ("query", "key", "value")], 3 * H)
+        ctx = _e((x.shape[0], 3 * H), BF, x.device) if pre3 else _e((x.shape[0], H), F32, x.device)
+        ops.attn_fwd_f32(q=qkv[:, :H], k=qkv[:, H:2 * H], v=qkv[:, 2 * H:], ctx=None if pre3 else ctx, ctx_split3=ctx if pre3 else None,
+                         B=B, nh=self.nh, D=64, Sq=S, Sk=S, scale=0.125, fast=True, **attn)
+        s1 = self.lin(ctx, [p + "attention.output.dense.weight"], [p + "attention.output.dense.bias"], H, res_f32=x)
+        a = self._ln(s1, p + "attention.output.LayerNorm.weight", p + "attention.output.LayerNorm.bias", self.eps)
+        f = self.lin(a, [p + "intermediate.dense.weight"], [p + "intermediate.dense.bias"], I, act=ops.ACT_GELU, split3=pre3)
+        s2 = self.lin(f, [p + "output.dense.weight"], [p + "output.dense.bias"], H, res_f32=a)
+        return self._ln(s2, p + "output.LayerNorm.weight", p + "output.LayerNorm.bias", self.eps)
+
+    @torch.no_grad()
+    def forward(self, input_ids, attention_mask, token_type_ids, pixel_values, sep_idx, visual_attention_mask=None):
+        from .visual_bert_engine import EMB, HEAD, VPROJ, WORD, vbert_mask_and_sep
+        st, H = self.st, self.H
+        dev = input_ids.device
+        B, L = input_ids.shape
+        V, Fd = int(pixel_values.shape[1]), int(pixel_values.shape[2])
+        S = L + V
+        M = B * S
+        pe = self.lin(pixel_values.contiguous().view(B * V, Fd), [VPROJ], [EMB + "visual_projection.bias"], H)
+        x = _e((M, H), F32, dev)
+        ops.vbert_embed_fwd(ids=input_ids, tt=token_type_ids, word=st.m(WORD), pos=st.m(EMB + "position_embeddings.weight"),
+                            type_=st.m(EMB + "token_type_embeddings.weight"), vpos=st.m(EMB + "visual_position_embeddings.weight")[0],
+                            vtype=st.m(EMB + "visual_token_type_embeddings.weight")[1], proj=pe, gamma=st.m(EMB + "LayerNorm.weight"),
+                            beta=st.m(EMB + "LayerNorm.bias"), eps=self.eps, B=B, L=L, V=V, H=H, x=x, s=_e((M, H), F32, dev),
+                            mean=_e((M,), F32, dev), rstd=_e((M,), F32, dev))
+        mask, sep = vbert_mask_and_sep(attention_mask, visual_attention_mask, sep_idx, V)
+        for l in range(self.nl):
+            p = f"visual_bert.encoder.layer.{l}."
+            x = self._block(p, x, B, S, attn_mask=mask, sep=sep, sep_stride=1, w0=st.m(p + "attention.self.adaptive_weight.0"),
+                            w1=st.m(p + "attention.self.adaptive_weight.1"), rw_row_lo=V + 1)
+        y = self.lin(x, [HEAD + "dense.weight"], [HEAD + "dense.bias"], H, act=ops.ACT_GELU)
+        trans = self._ln(y, HEAD + "LayerNorm.weight", HEAD + "LayerNorm.bias", self.eps)
+        return trans.view(B, S, H)

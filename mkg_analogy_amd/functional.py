@@ -367,6 +367,9 @@ class LazyLogits:
         pos = torch.empty(B, device=input_ids.device, dtype=torch.int32)
         row = torch.empty(B, device=input_ids.device, dtype=torch.int32)
         ops.find_token(input_ids.contiguous(), mask_token_id, pos, row, status=_status(input_ids.device))     # absent: row b*L+0 + status bit (check_status)
+        S = int(self.trans.shape[1])
+        if S != L:                                   # trans_hidden_states longer than the text (VisualBERT: [B, L + V, H]): rows are b * S + position
+            row = (row + torch.div(row, L, rounding_mode="floor") * (S - L)).to(torch.int32)
         return LazyRows(self, row)
 
     def materialize(self) -> torch.Tensor:

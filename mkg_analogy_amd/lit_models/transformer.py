@@ -87,6 +87,14 @@ class TransformerLitModel(BaseLitModel):
         q_head_idx = batch.pop("q_head_idx", None)
         a_head_idx = batch.pop("a_head_idx", None)
         input_ids = batch["input_ids"]
+        if "VisualBertKGC" in str(type(self.model)):
+            if self.args.pretrain:
+                raise NotImplementedError("VisualBertKGC has no MarKG pre-train step on the HIP path: the model needs sep_idx, which pre-train batches "
+                                          "do not carry (fine-tune only, scripts/run_finetune_visualbert.sh)")
+            # lit_models/transformer.py:98-102: trans_hidden_states covers [text | regions] and the relaxation-loss rows are read V rows further down
+            # (partly in region territory -- the reference's behaviour, reproduced); the [MASK] row is read unshifted.  New tensors: the batch keeps its own
+            img_len = int(batch["pixel_values"].shape[1])
+            rel_idx, q_head_idx, a_head_idx = rel_idx + img_len, q_head_idx + img_len, a_head_idx + img_len
         model_output = self.model(**batch, return_dict=True, **self._needed(input_ids, None if self.args.pretrain else (rel_idx, q_head_idx, a_head_idx)))
         logits = model_output[0].logits
         dev = logits.trans.device

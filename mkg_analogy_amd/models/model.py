@@ -25,3 +25,12 @@ class ViltKGC(__import__("mkg_analogy_amd.models.modeling_vilt", fromlist=["Vilt
     def add_to_argparse(parser):
         parser.add_argument("--pretrain", type=int, default=0, help="")
         return parser
+
+
+class VisualBertKGC(__import__("mkg_analogy_amd.models.modeling_visual_bert", fromlist=["VisualBertForMaskedLM"]).VisualBertForMaskedLM):
+    """MarT/models/model.py VisualBertKGC (fine-tune only: the reference cannot run the MarKG pre-train step without sep_idx)."""
+
+    @staticmethod
+    def add_to_argparse(parser):
+        parser.add_argument("--pretrain", type=int, default=0, help="")
+        return parser

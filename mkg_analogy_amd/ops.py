@@ -537,3 +537,30 @@ def vilt_embed_fwd(**kw):
 def vilt_embed_bwd(**kw):
     """ds_text, dpatch (un-permuted) written; every table gradient accumulated, in a fixed summation order."""
     _LIBM.check(_LIBM.lib().mart_vilt_embed_bwd(C.byref(_vilt_desc(**kw)), _stream()), "mart_vilt_embed_bwd")
+
+
+# ---------------------------------------------------------------- VisualBERT joint embedding (csrc/visual_bert.hip)
+def _vbert_desc(*, ids, tt, gamma, B, L, V, H, s, mean, rstd, p_drop=0.0, seed=0, word=None, pos=None, type_=None, vpos=None, vtype=None, proj=None,
+                beta=None, eps=0.0, x=None, x_bf16=None, x_f16=None, dx=None, ds_text=None, dproj=None, dgamma=None, dbeta=None, dpos=None,
+                dtype=None, dvpos=None, dvtype=None, ws=None):
+    assert ids.dtype == torch.int64 and tt.dtype == torch.int64 and tuple(ids.shape) == (B, L) and tuple(tt.shape) == (B, L)
+    assert proj is None or (proj.dtype == F32 and proj.numel() == B * V * H)
+    d = _LIBM.VbertEmbed()
+    d.ids, d.tt, d.word, d.pos, d.type, d.vpos, d.vtype, d.proj = _p(ids), _p(tt), _p(word), _p(pos), _p(type_), _p(vpos), _p(vtype), _p(proj)
+    d.gamma, d.beta, d.eps, d.p_drop, d.seed = _p(gamma), _p(beta), eps, p_drop, seed
+    d.B, d.L, d.V, d.H = B, L, V, H
+    d.x, d.x_bf16, d.x_f16, d.s, d.mean, d.rstd = _p(x), _p(x_bf16), _p(x_f16), _p(s), _p(mean), _p(rstd)
+    d.dx, d.ds_text, d.dproj = _p(dx), _p(ds_text), _p(dproj)
+    d.dgamma, d.dbeta, d.dpos, d.dtype, d.dvpos, d.dvtype = _p(dgamma), _p(dbeta), _p(dpos), _p(dtype), _p(dvpos), _p(dvtype)
+    d.ws, d.ws_bytes = _p(ws), (ws.numel() * 4 if ws is not None else 0)
+    return d
+
+
+def vbert_embed_fwd(**kw):
+    """x [B*(L+V), H] f32 (+ optional bf16 / fp16 copies) = dropout(LayerNorm([text | visual])) (include/mart_hip.h mart_vbert_embed_desc)."""
+    _LIBM.check(_LIBM.lib().mart_vbert_embed_fwd(C.byref(_vbert_desc(**kw)), _stream()), "mart_vbert_embed_fwd")
+
+
+def vbert_embed_bwd(**kw):
+    """ds_text, dproj written; every small-table gradient accumulated, in a fixed summation order.  ``ws``: (B * V + 4 (L + V)) * H floats."""
+    _LIBM.check(_LIBM.lib().mart_vbert_embed_bwd(C.byref(_vbert_desc(**kw)), _stream()), "mart_vbert_embed_bwd")
