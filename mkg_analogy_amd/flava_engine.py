@@ -100,6 +100,7 @@ class FlavaEngine:
         self.nt, self.ni, self.nm = tc.num_hidden_layers, ic.num_hidden_layers, mc.num_hidden_layers
         self.eps = float(tc.layer_norm_eps)
         self.grad_ready: Optional[Callable[[int], None]] = None
+        self.grad_ready_async: Optional[Callable] = None
         self.taps: Optional[dict] = None
         self.head_split = os.environ.get("MART_HEAD_SPLIT", "1") == "1"   # head transform + scoring GEMM on two-term operand splits (engine.UnimoEngine.head_split)
         # the forward linear layers of the TEXT and MULTIMODAL stacks on fp16 operands (same switch and reasoning as engine.UnimoEngine.text_f16:
@@ -312,7 +313,7 @@ class FlavaEngine:
         def notify(off):
             if self.grad_ready is not None:
                 self.grad_ready(off)
-            if getattr(self, "grad_ready_async", None) is not None:    # single-stream engine: nothing to wait for besides the current stream
+            if self.grad_ready_async is not None:                      # single-stream engine: nothing to wait for besides the current stream
                 self.grad_ready_async(off, [])
         xm, mmean, mrstd, mm_b, rows, y, zh, hm, hr = sv["head"]
         # head transform

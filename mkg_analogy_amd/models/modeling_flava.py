@@ -11,16 +11,17 @@ never evaluated, exactly as in the reference's MarT usage.  Sub-modules are para
 from __future__ import annotations
 
 from types import SimpleNamespace
-from typing import Dict, Optional
+from typing import Dict
 
 import torch
 from torch import nn
 
 from .. import functional as Fn
-from .. import ops
-from ..flava_engine import FlavaEngine, flava_f16_weight, flava_gemm_groups, flava_layout_order, FLAVA_DEAD
-from ..params import FlatStore, refresh_shadows_on_load
-from .modeling_unimo import MaskedLMOutput, _Container
+from ..engine_precise import PreciseFlavaForward, PreciseFlavaTrain
+from ..flava_engine import FLAVA_DEAD, WORD as FLAVA_WORD, FlavaEngine, flava_f16_weight, flava_gemm_groups, flava_layout_order
+from ..params import FlatStore
+from ._backbone import HipMaskedLM
+from .modeling_unimo import _Container
 
 
 class FlavaSelfAttention(_Container):
@@ -160,97 +161,29 @@ def flava_config(vocab_size=30522, hidden_size=768, text_layers=12, image_layers
         multimodal_config=SimpleNamespace(num_hidden_layers=mm_layers, **common), initializer_range=0.02)
 
 
-class FlavaForMaskedLM(nn.Module):
+class FlavaForMaskedLM(HipMaskedLM):
+    WORD, BIAS = FLAVA_WORD, "cls.bias"
+    ENGINE, PRECISE, PRECISE_TRAIN = FlavaEngine, PreciseFlavaForward, PreciseFlavaTrain
+    no_image_table = "FLAVA reads pixels from pixel_values; the device image table (image_index) is not built for this backbone"
+
     def __init__(self, config):
-        super().__init__()
+        super().__init__(config)
         for sub in (config.text_config, config.image_config, config.multimodal_config):
             if getattr(sub, "hidden_dropout_prob", 0.0) or getattr(sub, "attention_probs_dropout_prob", 0.0):
                 raise NotImplementedError("the HIP FLAVA path implements the facebook/flava-full configuration (all dropouts 0)")
-        self.config = config
         self.flava = FlavaModel(config)
         self.cls = FlavaMaskedPredictionHead(config.text_config)
-        self._store: Optional[FlatStore] = None
-        self._engine: Optional[FlavaEngine] = None
-        self.image_table = None
-        self.tie_weights()
-        refresh_shadows_on_load(self)
+        self._tie_and_hook()
 
-    # embedding surgery (same contract as the MKGformer class)
-    def get_input_embeddings(self):
-        return self.flava.text_model.embeddings.word_embeddings
+    @property
+    def initializer_range(self):
+        return self.config.text_config.initializer_range
 
-    def get_output_embeddings(self):
-        return self.cls.decoder
-
-    def tie_weights(self):
-        dec, emb = self.cls.decoder, self.get_input_embeddings()
-        dec.weight = emb.weight
-        if self.cls.bias.shape[0] != emb.weight.shape[0]:
-            nb = torch.zeros(emb.weight.shape[0], dtype=self.cls.bias.dtype, device=self.cls.bias.device)
-            n = min(nb.shape[0], self.cls.bias.shape[0])
-            nb[:n] = self.cls.bias.data[:n]
-            self.cls.bias = nn.Parameter(nb)
-        dec.bias = self.cls.bias
-        dec.out_features = emb.num_embeddings
-
-    def resize_token_embeddings(self, new_num_tokens):
-        old = self.get_input_embeddings()
-        if new_num_tokens is None or new_num_tokens == old.weight.shape[0]:
-            return
-        w = old.weight.data
-        new = nn.Embedding(new_num_tokens, w.shape[1]).to(device=w.device, dtype=w.dtype)
-        new.weight.data.normal_(mean=0.0, std=self.config.text_config.initializer_range)
-        n = min(w.shape[0], new_num_tokens)
-        new.weight.data[:n] = w[:n]
-        self.flava.text_model.embeddings.word_embeddings = new
-        self._store = self._engine = None
-        self.tie_weights()
-
-    def finalize(self, device=None) -> FlatStore:
-        if self._store is not None and self._store.still_bound():
-            return self._store
-        named = dict(self.named_parameters())
-        if self._store is not None and self._store.owns(named):
-            self._store.bind(self)
-            return self._store
-        ops.require_gpu()
-        if device is None:
-            p0 = next(iter(named.values()))
-            device = p0.device if p0.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    def _make_store(self, named, device):
         c = self.config
         nl = (c.text_config.num_hidden_layers, c.image_config.num_hidden_layers, c.multimodal_config.num_hidden_layers)
-        self._store = FlatStore(named, 0, torch.device(device), order=flava_layout_order(*nl), gemm_groups=flava_gemm_groups(*nl), dead=FLAVA_DEAD(nl),
-                                f16_weight=flava_f16_weight)
-        self.tie_weights()
-        self._engine = FlavaEngine(self._store, c)
-        self._anchor = torch.zeros(1, device=device, requires_grad=True)
-        if not hasattr(self, "base_seed"):       # a re-finalize (resize_token_embeddings) keeps the rank-hashed seed and the step counter
-            self._step = 0
-            self.base_seed = 0x5EED      # dropout stream; distributed.GradSync hashes the rank into it
-        if not hasattr(self, "precision"):
-            self.precision = "bf16"
-        self._store.bind(self)
-        return self._store
-
-    @property
-    def store(self) -> FlatStore:
-        return self.finalize()
-
-    @property
-    def engine(self) -> FlavaEngine:
-        self.finalize()
-        return self._engine
-
-    def sync_shadows(self):
-        self.finalize().refresh_shadows()
-
-    def set_precision(self, precision: str):
-        """"bf16" (training + eval) or "fp32" (evaluation only: fp32 activations, split-bf16 MFMA contractions, fp32 attention;
-        engine_precise.PreciseFlavaForward)."""
-        if precision not in ("bf16", "fp32"):
-            raise ValueError("precision must be 'bf16' or 'fp32'")
-        self.precision = precision
-        return self
+        return FlatStore(named, 0, device, order=flava_layout_order(*nl), gemm_groups=flava_gemm_groups(*nl), dead=FLAVA_DEAD(nl),
+                         f16_weight=flava_f16_weight)
 
     def forward(self, input_ids=None, pixel_values=None, attention_mask=None, token_type_ids=None, bool_masked_pos=None, position_ids=None,
                 image_attention_mask=None, skip_multimodal_encoder=None, output_attentions=None, output_hidden_states=True, return_dict=None,
@@ -259,51 +192,30 @@ class FlavaForMaskedLM(nn.Module):
             raise NotImplementedError("MarT never passes these FlavaForMaskedLM arguments; unsupported on the HIP path")
         st = self.finalize()
         dev = st.device
-        input_ids = input_ids.to(dev, torch.int64).contiguous()
-        B, L = input_ids.shape
-        attention_mask = torch.ones((B, L), device=dev, dtype=torch.int64) if attention_mask is None else attention_mask.to(dev, torch.int64).contiguous()
-        token_type_ids = torch.zeros((B, L), device=dev, dtype=torch.int64) if token_type_ids is None else token_type_ids.to(dev, torch.int64).contiguous()
-        if sep_idx is not None:
-            sep_idx = sep_idx.to(dev, torch.int64).contiguous()
+        input_ids, attention_mask, token_type_ids, sep_idx = self._text_inputs(dev, input_ids, attention_mask, token_type_ids, sep_idx)
         pixel_values = pixel_values.to(dev, torch.float32)
-        if getattr(self, "precision", "bf16") == "fp32":
+        if self.precision == "fp32":
             st.join_pending()
             if labels is not None:
                 raise NotImplementedError("precision='fp32': no full-vocabulary labels path; score slices of .logits instead")
             if torch.is_grad_enabled():
                 # verification mode: fp32-accurate forward AND backward (engine_precise.PreciseFlavaTrain); eval-mode gradients
-                prt = getattr(self, "_precise_train", None)
-                if prt is None or prt.st is not st:
-                    from ..engine_precise import PreciseFlavaTrain
-                    prt = self._precise_train = PreciseFlavaTrain(st, self.config)
-                holder: Dict[str, torch.Tensor] = {}
-                trans = Fn._MKGformerFn.apply(self._anchor, prt, input_ids, attention_mask, token_type_ids, pixel_values, sep_idx, False, 0, holder)
-                out = MaskedLMOutput(loss=None, logits=Fn.LazyLogits(trans, None, st, word_name="flava.text_model.embeddings.word_embeddings.weight",
-                                                                     bias_name="cls.bias", precise=prt), hidden_states=None, attentions=None)
-                return (out, trans) if return_dict else ((out.logits,), trans)
+                pr = self._fp32_engine(train=True)
+                trans = Fn._MKGformerFn.apply(self._anchor, pr, input_ids, attention_mask, token_type_ids, pixel_values, sep_idx, False, 0, {})
+                return self._pack(trans, self._logits(trans, None, precise=pr), return_dict)
             if self.training:
                 raise NotImplementedError("precision='fp32' under no_grad is the evaluation path: call model.eval() (or set_precision('bf16'))")
-            pr = getattr(self, "_precise", None)
-            if pr is None or pr.st is not st:
-                from ..engine_precise import PreciseFlavaForward
-                pr = self._precise = PreciseFlavaForward(st, self.config)
+            pr = self._fp32_engine()
             trans = pr.forward(input_ids, attention_mask, token_type_ids, pixel_values, sep_idx)
-            out = MaskedLMOutput(loss=None, logits=Fn.LazyLogits(trans, None, st, word_name="flava.text_model.embeddings.word_embeddings.weight",
-                                                                 bias_name="cls.bias", precise=pr), hidden_states=None, attentions=None)
-            return (out, trans) if return_dict else ((out.logits,), trans)
-        self._step += 1
+            return self._pack(trans, self._logits(trans, None, precise=pr), return_dict)
         holder: Dict[str, torch.Tensor] = {}
         self._engine.save_for_backward = torch.is_grad_enabled()
         trans = Fn._MKGformerFn.apply(self._anchor, self._engine, input_ids, attention_mask, token_type_ids, pixel_values, sep_idx,
-                                      bool(self.training), (self.base_seed * 1000003 + self._step * 7919) & 0x7FFFFFFFFFFF, holder)
+                                      bool(self.training), self._next_seed(), holder)
         st.join_pending()                           # gradient zero-fill / W^T refresh issued next to this forward pass (optim.FusedAdamW)
-        logits = Fn.LazyLogits(trans, holder["trans_bf16"], st, word_name="flava.text_model.embeddings.word_embeddings.weight",
-                               bias_name="cls.bias", head_split=self._engine.head_split)
+        logits = self._logits(trans, holder["trans_bf16"], head_split=self._engine.head_split)
         loss = None
         if labels is not None:
             full = logits.materialize()
             loss = torch.nn.functional.cross_entropy(full.view(-1, full.shape[-1]), labels.to(dev).view(-1))
-        out = MaskedLMOutput(loss=loss, logits=logits, hidden_states=None, attentions=None)
-        if not return_dict:
-            return ((loss, logits) if loss is not None else (logits,)), trans
-        return out, trans
+        return self._pack(trans, logits, return_dict, loss=loss)

@@ -12,16 +12,16 @@ without the HIP library or a gfx950 device ``forward`` raises -- there is no eag
 """
 from __future__ import annotations
 
-from types import SimpleNamespace
-from typing import Dict, Optional
+from typing import Dict
 
 import torch
 from torch import nn
 
 from .. import functional as Fn
-from .. import ops
 from ..engine import UnimoEngine
-from ..params import FlatStore, refresh_shadows_on_load
+from ..engine_precise import PreciseUnimoForward, PreciseUnimoTrain
+from ..params import FlatStore
+from ._backbone import HipMaskedLM
 
 
 class _Container(nn.Module):
@@ -169,124 +169,27 @@ class UnimoOnlyMLMHead(_Container):
         self.predictions = UnimoLMPredictionHead(c)
 
 
-class MaskedLMOutput(SimpleNamespace):
-    """Duck-type of transformers.modeling_outputs.MaskedLMOutput: ``out.logits`` and ``out[0]`` style access."""
-
-    def __getitem__(self, i):
-        return [v for v in (self.loss, self.logits, self.hidden_states, self.attentions) if v is not None][i]
-
-
-class UnimoForMaskedLM(nn.Module):
+class UnimoForMaskedLM(HipMaskedLM):
+    WORD, BIAS = Fn.WORD, Fn.BIAS
+    ENGINE, PRECISE, PRECISE_TRAIN = UnimoEngine, PreciseUnimoForward, PreciseUnimoTrain
     accepts_needed_rows = True                      # forward(needed_rows=...): last-layer row subset
 
     def __init__(self, vision_config, text_config):
-        super().__init__()
+        super().__init__(text_config)
         self.unimo = UnimoModel(vision_config, text_config)
         self.cls = UnimoOnlyMLMHead(text_config)
-        self.config = text_config
         self.vision_config = vision_config
-        self._store: Optional[FlatStore] = None
-        self._engine: Optional[UnimoEngine] = None
-        self._step = 0
-        self.image_table = None                     # optional resident [N_img,3,S,S] f32 table for device-side batch assembly
-        self.base_seed = 0x5EED
-        self.precision = "bf16"                     # "fp32": fp32-accurate evaluation path (engine_precise), forward only
-        self._precise = None
-        self._precise_train = None
+        self._cfgs = (vision_config, text_config)
         self._mask_index: dict = {}                  # (device, B, nr) -> compact indices of slot 0 (row-subset passes)
-        self.tie_weights()
-        refresh_shadows_on_load(self)
+        self._tie_and_hook()
 
-    # ------------------------------------------------------------------ embedding surgery (modeling_unimo.py:895-930)
-    def get_input_embeddings(self):
-        return self.unimo.text_embeddings.word_embeddings
+    def _make_store(self, named, device):
+        return FlatStore(named, self.config.num_hidden_layers, device)
 
-    def get_output_embeddings(self):
-        return self.cls.predictions.decoder
-
-    def set_output_embeddings(self, new_embeddings):
-        self.cls.predictions.decoder = new_embeddings
-
-    def tie_weights(self):
-        dec, emb = self.get_output_embeddings(), self.get_input_embeddings()
-        dec.weight = emb.weight
-        pred = self.cls.predictions
-        if pred.bias.shape[0] != emb.weight.shape[0]:                   # zero-pad / truncate the decoder bias on resize
-            nb = torch.zeros(emb.weight.shape[0], dtype=pred.bias.dtype, device=pred.bias.device)
-            n = min(nb.shape[0], pred.bias.shape[0])
-            nb[:n] = pred.bias.data[:n]
-            pred.bias = nn.Parameter(nb)
-        dec.bias = pred.bias
-        dec.out_features = emb.num_embeddings
-
-    def resize_token_embeddings(self, new_num_tokens):
-        old = self.get_input_embeddings()
-        if new_num_tokens is None or new_num_tokens == old.weight.shape[0]:
-            return
-        w = old.weight.data
-        new = nn.Embedding(new_num_tokens, w.shape[1]).to(device=w.device, dtype=w.dtype)
-        new.weight.data.normal_(mean=0.0, std=self.config.initializer_range)   # _init_text_weights, :768-771
-        n = min(w.shape[0], new_num_tokens)
-        new.weight.data[:n] = w[:n]
-        self.unimo.text_embeddings.word_embeddings = new
-        self._store = self._engine = None
-        self.tie_weights()
-
-    # ------------------------------------------------------------------ flat storage / engine
-    def _named(self) -> Dict[str, nn.Parameter]:
-        return dict(self.named_parameters())          # tied decoder weight/bias are deduplicated by torch
-
-    def finalize(self, device=None) -> FlatStore:
-        """Move the parameters into the flat fp32/bf16 buffers the kernels use (idempotent)."""
-        if self._store is not None and self._store.still_bound():
-            return self._store
-        named = self._named()
-        if self._store is not None and self._store.owns(named):
-            self._store.bind(self)
-            return self._store
-        ops.require_gpu()
-        if device is None:
-            p0 = next(iter(named.values()))
-            device = p0.device if p0.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        self._store = FlatStore(named, self.config.num_hidden_layers, torch.device(device))
-        self.tie_weights()
-        for b in ("unimo.vision_embeddings.position_ids", "unimo.text_embeddings.position_ids"):
-            mod, _, name = b.rpartition(".")
-            m = self.get_submodule(mod)
-            m._buffers[name] = m._buffers[name].to(device)
-        self._engine = UnimoEngine(self._store, self.vision_config, self.config)
-        self._anchor = torch.zeros(1, device=device, requires_grad=True)
-        self._store.bind(self)
-        return self._store
-
-    @property
-    def store(self) -> FlatStore:
-        return self.finalize()
-
-    @property
-    def engine(self) -> UnimoEngine:
-        self.finalize()
-        return self._engine
-
-    def set_precision(self, precision: str):
-        """"bf16" (default: bf16 MFMA operands, fp32 accumulation / residual streams; training + eval) or "fp32"
-        (fp32 activations, split-bf16 MFMA contractions, fp32 attention -- meets the reference's fp32 results to ~1e-4 on
-        logits; evaluation under no_grad, and a verification-mode training step (eval-mode gradients, no dropout replay) when
-        gradients are enabled; see engine_precise.py)."""
-        if precision not in ("bf16", "fp32"):
-            raise ValueError("precision must be 'bf16' or 'fp32'")
-        self.precision = precision
-        return self
-
-    def set_image_table(self, table: torch.Tensor):
-        """Keep the per-entity pixel tensor (MarT/tools/encode_images_data.py output, data_module.py:209) resident in HBM so
-        that batches carry [B,2] row indices instead of 1.2 MB of pixels per example."""
-        st = self.finalize()
-        self.image_table = table.to(st.device, torch.float32).contiguous()
-
-    def sync_shadows(self):
-        """Call after editing parameters in place (e.g. _init_relation_word) so the bf16 GEMM operands follow."""
-        self.finalize().refresh_shadows()
+    def _make_engine(self, store):
+        for m in (self.unimo.vision_embeddings, self.unimo.text_embeddings):
+            m._buffers["position_ids"] = m._buffers["position_ids"].to(store.device)
+        return super()._make_engine(store)
 
     # ------------------------------------------------------------------ forward (modeling_unimo.py:848-893)
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None, sep_idx=None,
@@ -305,20 +208,9 @@ class UnimoForMaskedLM(nn.Module):
             raise NotImplementedError("position_ids / head_mask are unused by MarT (modeling_unimo.py:78-80) and unsupported here")
         st = self.finalize()
         dev = st.device
-        input_ids = input_ids.to(dev, torch.int64).contiguous()
+        input_ids, attention_mask, token_type_ids, sep_idx = self._text_inputs(dev, input_ids, attention_mask, token_type_ids, sep_idx)
         B, L = input_ids.shape
-        attention_mask = torch.ones((B, L), device=dev, dtype=torch.int64) if attention_mask is None else attention_mask.to(dev, torch.int64).contiguous()
-        token_type_ids = torch.zeros((B, L), device=dev, dtype=torch.int64) if token_type_ids is None else token_type_ids.to(dev, torch.int64).contiguous()
-        if sep_idx is not None:
-            sep_idx = sep_idx.to(dev, torch.int64).contiguous()
-        image_table = None
-        if image_index is not None:                 # device-side batch assembly (mkg_analogy_amd.batching.DeviceImageTable)
-            if self.image_table is None:
-                raise ValueError("image_index given but no image table attached: call model.set_image_table(table) first")
-            image_table = self.image_table
-            image_index = image_index.to(dev, torch.int32).contiguous()
-        else:
-            pixel_values = pixel_values.to(dev, torch.float32)
+        pixel_values, image_table, image_index = self._image_inputs(dev, pixel_values, image_index)
         train = bool(self.training)
         if self.precision == "fp32":
             st.join_pending()                       # (the fp32-accurate engines read W^T / write gradients from their first kernels on)
@@ -326,25 +218,16 @@ class UnimoForMaskedLM(nn.Module):
                 raise NotImplementedError("precision='fp32': no full-vocabulary labels path; score slices of .logits instead")
             if torch.is_grad_enabled():
                 # verification mode: fp32-accurate forward AND backward (engine_precise.PreciseUnimoTrain); eval-mode gradients only
-                if self._precise_train is None or self._precise_train.st is not st:
-                    from ..engine_precise import PreciseUnimoTrain
-                    self._precise_train = PreciseUnimoTrain(st, self.vision_config, self.config)
-                holder: Dict[str, torch.Tensor] = {}
-                trans = Fn._MKGformerFn.apply(self._anchor, self._precise_train, input_ids, attention_mask, token_type_ids, pixel_values, sep_idx,
-                                              train, 0, holder, image_table, image_index)
-                out = MaskedLMOutput(loss=None, logits=Fn.LazyLogits(trans, None, st, precise=self._precise_train), hidden_states=None, attentions=None)
-                return (out, trans) if return_dict else ((out.logits,), trans)
+                pr = self._fp32_engine(train=True)
+                trans = Fn._MKGformerFn.apply(self._anchor, pr, input_ids, attention_mask, token_type_ids, pixel_values, sep_idx,
+                                              train, 0, {}, image_table, image_index)
+                return self._pack(trans, self._logits(trans, None, precise=pr), return_dict)
             if train:
                 raise NotImplementedError("precision='fp32' under no_grad is the evaluation path: call model.eval() (or set_precision('bf16'))")
-            if self._precise is None or self._precise.st is not st:
-                from ..engine_precise import PreciseUnimoForward
-                self._precise = PreciseUnimoForward(st, self.vision_config, self.config)
-            trans = self._precise.forward(input_ids, attention_mask, token_type_ids, pixel_values, sep_idx, image_table=image_table,
-                                          image_index=image_index)
-            out = MaskedLMOutput(loss=None, logits=Fn.LazyLogits(trans, None, st, precise=self._precise), hidden_states=None, attentions=None)
-            return (out, trans) if return_dict else ((out.logits,), trans)
-        self._step += 1
-        seed = (self.base_seed * 1000003 + self._step * 7919) & 0x7FFFFFFFFFFF
+            pr = self._fp32_engine()
+            trans = pr.forward(input_ids, attention_mask, token_type_ids, pixel_values, sep_idx, image_table=image_table, image_index=image_index)
+            return self._pack(trans, self._logits(trans, None, precise=pr), return_dict)
+        seed = self._next_seed()
         holder: Dict[str, torch.Tensor] = {}
         self._engine.save_for_backward = torch.is_grad_enabled()
         rows = mask_row = None
@@ -385,13 +268,9 @@ class UnimoForMaskedLM(nn.Module):
                                    mask_token=getattr(needed_rows, "_mart_mask_token", None))
             trans = Fn._DenseRowsFn.apply(trans, rows, B, L)            # the reference's [B, L, H] tensor: promised rows filled in, NaN elsewhere
             trans._mart_rows = compact
-        logits = Fn.LazyLogits(trans, holder["trans_bf16"] if compact is None else None, st, head_split=self._engine.head_split, valid_rows=rows,
-                               compact=compact)
+        logits = self._logits(trans, holder["trans_bf16"] if compact is None else None, head_split=self._engine.head_split, valid_rows=rows, compact=compact)
         loss = None
         if labels is not None:                      # CrossEntropyLoss over the full vocabulary (:880-882); not used by MarT
             full = logits.materialize()
             loss = torch.nn.functional.cross_entropy(full.view(-1, full.shape[-1]), labels.to(dev).view(-1))
-        out = MaskedLMOutput(loss=loss, logits=logits, hidden_states=hidden_states, attentions=None)
-        if not return_dict:
-            return tuple(v for v in (loss, logits, hidden_states) if v is not None), trans
-        return out, trans
+        return self._pack(trans, logits, return_dict, loss=loss, hidden_states=hidden_states)

@@ -10,16 +10,17 @@ containers; compute is in ``mkg_analogy_amd.visual_bert_engine``.  ``pixel_value
 from __future__ import annotations
 
 from types import SimpleNamespace
-from typing import Dict, Optional
+from typing import Dict
 
 import torch
 from torch import nn
 
 from .. import functional as Fn
-from .. import ops
-from ..params import FlatStore, refresh_shadows_on_load
-from ..visual_bert_engine import BIAS, WORD, VisualBertEngine, vbert_f16_weight, vbert_gemm_groups, vbert_layout_order
-from .modeling_unimo import BertOutput, BertSelfOutput, MaskedLMOutput, UnimoOnlyMLMHead, _Container
+from ..engine_precise import PreciseVisualBertForward
+from ..params import FlatStore
+from ..visual_bert_engine import BIAS as VBERT_BIAS, WORD as VBERT_WORD, VisualBertEngine, vbert_f16_weight, vbert_gemm_groups, vbert_layout_order
+from ._backbone import HipMaskedLM
+from .modeling_unimo import BertOutput, BertSelfOutput, UnimoOnlyMLMHead, _Container
 
 
 class VisualBertEmbeddings(_Container):
@@ -94,105 +95,24 @@ def visual_bert_config(vocab_size=30522, hidden_size=768, num_hidden_layers=12, 
                            bypass_transformer=False, special_visual_initialize=True, pad_token_id=1)
 
 
-class VisualBertForMaskedLM(nn.Module):
+class VisualBertForMaskedLM(HipMaskedLM):
+    WORD, BIAS = VBERT_WORD, VBERT_BIAS
+    ENGINE, PRECISE = VisualBertEngine, PreciseVisualBertForward  # fp32 training (verification mode) is not built for VisualBERT
+    no_image_table = "VisualBERT reads region features from pixel_values [B, 72, 2048]; the device image table (image_index) holds pixels only"
+
     def __init__(self, config):
-        super().__init__()
+        super().__init__(config)
         if getattr(config, "bypass_transformer", False):
             raise NotImplementedError("the HIP VisualBERT path implements bypass_transformer=False (the VisualBertConfig default)")
         if getattr(config, "hidden_act", "gelu") != "gelu":
             raise NotImplementedError("the HIP VisualBERT path implements erf GELU")
-        self.config = config
         self.visual_bert = VisualBertModel(config)
         self.cls = UnimoOnlyMLMHead(config)
-        self._store: Optional[FlatStore] = None
-        self._engine: Optional[VisualBertEngine] = None
-        self.tie_weights()
-        refresh_shadows_on_load(self)
+        self._tie_and_hook()
 
-    # embedding surgery (same contract as the other backbones)
-    def get_input_embeddings(self):
-        return self.visual_bert.embeddings.word_embeddings
-
-    def get_output_embeddings(self):
-        return self.cls.predictions.decoder
-
-    def set_output_embeddings(self, new_embeddings):
-        self.cls.predictions.decoder = new_embeddings
-        self.tie_weights()
-
-    def tie_weights(self):
-        pred, emb = self.cls.predictions, self.get_input_embeddings()
-        pred.decoder.weight = emb.weight
-        if pred.bias.shape[0] != emb.weight.shape[0]:
-            nb = torch.zeros(emb.weight.shape[0], dtype=pred.bias.dtype, device=pred.bias.device)
-            n = min(nb.shape[0], pred.bias.shape[0])
-            nb[:n] = pred.bias.data[:n]
-            pred.bias = nn.Parameter(nb)
-        pred.decoder.bias = pred.bias
-        pred.decoder.out_features = emb.num_embeddings
-
-    def resize_token_embeddings(self, new_num_tokens):
-        old = self.get_input_embeddings()
-        if new_num_tokens is None or new_num_tokens == old.weight.shape[0]:
-            return
-        w = old.weight.data
-        new = nn.Embedding(new_num_tokens, w.shape[1]).to(device=w.device, dtype=w.dtype)
-        new.weight.data.normal_(mean=0.0, std=self.config.initializer_range)
-        n = min(w.shape[0], new_num_tokens)
-        new.weight.data[:n] = w[:n]
-        self.visual_bert.embeddings.word_embeddings = new
-        self._store = self._engine = None
-        self.tie_weights()
-
-    def finalize(self, device=None) -> FlatStore:
-        if self._store is not None and self._store.still_bound():
-            return self._store
-        named = dict(self.named_parameters())
-        if self._store is not None and self._store.owns(named):
-            self._store.bind(self)
-            return self._store
-        ops.require_gpu()
-        if device is None:
-            p0 = next(iter(named.values()))
-            device = p0.device if p0.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    def _make_store(self, named, device):
         n = self.config.num_hidden_layers
-        self._store = FlatStore(named, 0, torch.device(device), order=vbert_layout_order(n), gemm_groups=vbert_gemm_groups(n), dead=(),
-                                f16_weight=vbert_f16_weight)
-        self.tie_weights()
-        self._engine = VisualBertEngine(self._store, self.config)
-        self._precise = None
-        self._anchor = torch.zeros(1, device=device, requires_grad=True)
-        if not hasattr(self, "base_seed"):
-            self._step = 0
-            self.base_seed = 0x5EED
-        if not hasattr(self, "precision"):
-            self.precision = "bf16"
-        self._store.bind(self)
-        return self._store
-
-    @property
-    def store(self) -> FlatStore:
-        return self.finalize()
-
-    @property
-    def engine(self) -> VisualBertEngine:
-        self.finalize()
-        return self._engine
-
-    def sync_shadows(self):
-        self.finalize().refresh_shadows()
-
-    def set_image_table(self, table):
-        raise NotImplementedError("VisualBERT reads region features from pixel_values [B, 72, 2048]; the device image table (image_index) holds "
-                                  "pixels only")
-
-    def set_precision(self, precision: str):
-        """"bf16" (training + eval) or "fp32" (evaluation only: fp32 activations, split-bf16 MFMA contractions, fp32 attention;
-        engine_precise.PreciseVisualBertForward).  fp32 training (verification mode) is not built for VisualBERT."""
-        if precision not in ("bf16", "fp32"):
-            raise ValueError("precision must be 'bf16' or 'fp32'")
-        self.precision = precision
-        return self
+        return FlatStore(named, 0, device, order=vbert_layout_order(n), gemm_groups=vbert_gemm_groups(n), dead=(), f16_weight=vbert_f16_weight)
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None, inputs_embeds=None,
                 pixel_values=None, visual_attention_mask=None, visual_token_type_ids=None, labels=None, output_attentions=None,
@@ -205,7 +125,7 @@ class VisualBertForMaskedLM(nn.Module):
             raise TypeError("unsupported operand type(s) for +=: 'NoneType' and 'int' (VisualBERT needs sep_idx: no MarKG pre-train step)")
         if pixel_values is None:
             raise ValueError("VisualBERT needs pixel_values: region features [B, V, visual_embedding_dim]")
-        fp32 = getattr(self, "precision", "bf16") == "fp32"
+        fp32 = self.precision == "fp32"
         if fp32 and (torch.is_grad_enabled() or self.training):
             raise NotImplementedError("precision='fp32' is the VisualBERT evaluation path (model.eval() under torch.no_grad()); "
                                       "fp32 training (verification mode) is not built for VisualBERT")
@@ -213,37 +133,22 @@ class VisualBertForMaskedLM(nn.Module):
             raise NotImplementedError("precision='fp32': no full-vocabulary labels path; score slices of .logits instead")
         st = self.finalize()
         dev = st.device
-        input_ids = input_ids.to(dev, torch.int64).contiguous()
-        B, L = input_ids.shape
-        attention_mask = torch.ones((B, L), device=dev, dtype=torch.int64) if attention_mask is None else attention_mask.to(dev, torch.int64).contiguous()
-        token_type_ids = torch.zeros((B, L), device=dev, dtype=torch.int64) if token_type_ids is None else token_type_ids.to(dev, torch.int64).contiguous()
-        sep_idx = sep_idx.to(dev, torch.int64).contiguous()              # (a copy when it lives elsewhere; the engine never writes to it)
+        input_ids, attention_mask, token_type_ids, sep_idx = self._text_inputs(dev, input_ids, attention_mask, token_type_ids, sep_idx)
         pixel_values = pixel_values.to(dev, torch.float32).contiguous()
         if visual_attention_mask is not None:
             visual_attention_mask = visual_attention_mask.to(dev)
         if fp32:
             st.join_pending()
-            pr = getattr(self, "_precise", None)
-            if pr is None or pr.st is not st:
-                from ..engine_precise import PreciseVisualBertForward
-                pr = self._precise = PreciseVisualBertForward(st, self.config)
+            pr = self._fp32_engine()
             trans = pr.forward(input_ids, attention_mask, token_type_ids, pixel_values, sep_idx, visual_attention_mask)
-            out = MaskedLMOutput(loss=None, logits=Fn.LazyLogits(trans, None, st, word_name=WORD, bias_name=BIAS, precise=pr),
-                                 hidden_states=None, attentions=None)
-            return (out, trans) if return_dict else ((out.logits,), trans)
+            return self._pack(trans, self._logits(trans, None, precise=pr), return_dict)
         self._engine.visual_mask = visual_attention_mask
-        self._step += 1
         holder: Dict[str, torch.Tensor] = {}
         self._engine.save_for_backward = torch.is_grad_enabled()
         trans = Fn._MKGformerFn.apply(self._anchor, self._engine, input_ids, attention_mask, token_type_ids, pixel_values, sep_idx,
-                                      bool(self.training), (self.base_seed * 1000003 + self._step * 7919) & 0x7FFFFFFFFFFF, holder, None, None)
+                                      bool(self.training), self._next_seed(), holder, None, None)
         st.join_pending()
-        logits = Fn.LazyLogits(trans, holder["trans_bf16"], st, word_name=WORD, bias_name=BIAS, head_split=self._engine.head_split)
-        loss = None
         if labels is not None:
             raise NotImplementedError("labels are [B, L] while the logits cover L + V rows (the reference's CrossEntropyLoss fails on the shapes too); "
                                       "score slices of .logits instead")
-        out = MaskedLMOutput(loss=loss, logits=logits, hidden_states=None, attentions=None)
-        if not return_dict:
-            return (logits,), trans
-        return out, trans
+        return self._pack(trans, self._logits(trans, holder["trans_bf16"], head_split=self._engine.head_split), return_dict)

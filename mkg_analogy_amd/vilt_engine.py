@@ -87,6 +87,7 @@ class ViltEngine:
         self.eps = float(config.layer_norm_eps)
         self.n_tpos = int(config.max_position_embeddings)
         self.grad_ready: Optional[Callable[[int], None]] = None
+        self.grad_ready_async: Optional[Callable] = None
         self.taps: Optional[dict] = None
         self.grad_stream_bf16 = True
         # forward products on fp16 operands (FlavaEngine.f16: LayerNorm outputs, contexts and GELU outputs rounded 8x finer than bf16 at the
@@ -197,7 +198,7 @@ class ViltEngine:
         def notify(off):
             if self.grad_ready is not None:
                 self.grad_ready(off)
-            if getattr(self, "grad_ready_async", None) is not None:
+            if self.grad_ready_async is not None:
                 self.grad_ready_async(off, [])
         x, xmean, xrstd, xb, rows, y, zh, hm, hr = sv["head"]
         # head transform
