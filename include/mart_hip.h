@@ -169,7 +169,8 @@ int mart_gather_images(const float* table, const int32_t* index, float* out, int
 /* tail_shift: position row of the second image's patch t is t - tail_shift (MKGformer 0: pos[1..P]; FLAVA 1: pos[0..P-1],
  * the reference's FlavaImageEmbeddings quirk, modeling_flava.py:338) */
 int mart_vision_assemble(const void* patch_bf16, const float* cls, const float* pos, float* s, int B, int P, int H, int tail_shift, void* stream);
-/* backward of the assemble: dpatch (bf16) and atomically accumulated dcls, dpos */
+/* backward of the assemble: dpatch (bf16) and atomically accumulated dcls, dpos.  NULL rule (all parameter-gradient outputs of this library): a
+ * NULL dpatch / dcls / dpos is "frozen, do not compute"; at least one must be given. */
 int mart_vision_assemble_bwd(const float* ds, void* dpatch_bf16, float* dcls, float* dpos, int B, int P, int H, int tail_shift, void* stream);
 /* same result, deterministic: slice partials through a caller-owned workspace ((P+1) * 16 * 2 * H floats), reduced in slice order */
 int mart_vision_assemble_bwd_det(const float* ds, void* dpatch_bf16, float* dcls, float* dpos, int B, int P, int H, int tail_shift,
@@ -188,7 +189,8 @@ typedef struct {
 int mart_text_embed_fwd(const mart_text_embed_desc* d, void* stream);
 /* dy*dropmask/(1-p) -> dyd (f32) : first half of the text-embedding backward (LN bwd follows) */
 int mart_dropout_bwd_f32(const float* dy_f32, const void* dy_bf16, float* out, long long n, float p, uint64_t seed, void* stream);
-/* scatter ds [B*L,H] into dword[ids], dpos[0..L), dtype[tt] (atomic) */
+/* scatter ds [B*L,H] into dword[ids], dpos[0..L), dtype[tt] (atomic).  Each of dword / dpos / dtype may be NULL on its own (a frozen table: its
+ * rows are not computed); at least one must be given.  The _det form follows the same rule (order / meta are needed for dword only). */
 int mart_text_embed_scatter(const float* ds, const int64_t* ids, const int64_t* tt, float* dword, float* dpos, float* dtype,
                             int B, int L, int H, void* stream);
 /* same result, deterministic (no float atomics).  order[B*L]: the flat token positions sorted by id (stable sort of ids; index
@@ -305,7 +307,8 @@ int mart_fusion_fwd(const mart_fusion_fwd_desc* d, void* stream);
 /* autograd of the three lines above: dq = d(hidden) (bf16, written), dv_f32 += d(visual) in place (the vision-stream gradient; each
  * element is updated by one wave per launch and the 64-query blocks are sequential launches: no atomics, fixed order),
  * dv_bf16 = optional bf16 copy of the updated rows.  dv_f32 == NULL (round 6): the vision-stream gradient is carried in bf16 and dv_bf16 itself is
- * read, updated and written (f32 arithmetic, one rounding). */
+ * read, updated and written (f32 arithmetic, one rounding).  dv_f32 == NULL AND dv_bf16 == NULL: d(visual) is not computed (nothing upstream of
+ * the visual operand is trainable); dq is the same arithmetic either way. */
 typedef struct {
   const void* q; int ldq; const void* v; int ldv;
   const void* dout; int lddo;                                       /* d(fusion_output) bf16 [B*Lq, H] */
@@ -402,7 +405,9 @@ int mart_dropout_mask(uint8_t* out, long long n, float p, uint64_t seed, void* s
 /* ---------------------------------------------------------------- optimizer (lit_models/transformer.py:224-241)
  * Multi-tensor AdamW over the flat parameter buffer; also refreshes the bf16 shadow the GEMMs read.
  * chunks: int32 triples (start, length, flags), start/length in elements; flags bit 0 = weight decay applies, bit 1 = the chunk also
- * refreshes the fp16 shadow (forward weights of the text stream, engine.text_f16). */
+ * refreshes the fp16 shadow (forward weights of the text stream, engine.text_f16), bit 2 (value 4) = zero-only: a frozen tensor whose
+ * gradient some launch still writes -- with zero_grad its gradient elements are written back as 0, and master, m, v and the shadows are
+ * not touched (without zero_grad the chunk does nothing); bits 0 and 1 are ignored for such a chunk. */
 typedef struct {
   float* master; float* grad /* read; written (zeros) only with zero_grad */; float* m; float* v; void* shadow_bf16;
   const int32_t* chunks; int n_chunks;

@@ -369,8 +369,11 @@ __global__ __launch_bounds__(FT, 1) void fusion_bwd_k(mart_fusion_bwd_desc p, in
   const bool gb16 = p.dv_f32 == nullptr;
   float* dvf = gb16 ? nullptr : p.dv_f32 + (long long)g.b * p.Nv * p.lddv + rcol;
   bf16* dvb = p.dv_bf16 ? (bf16*)p.dv_bf16 + (long long)g.b * p.Nv * p.lddvb + rcol : nullptr;
-  stage4(0, st0);
-  for (int dc = 0; dc < ((dbg & 4) ? 0 : g.NDC); ++dc) {
+  // dv_f32 == NULL and dv_bf16 == NULL: nothing upstream of the visual operand is trainable -- B4 is not computed (and its first Q / dO chunk not staged:
+  // B3 reuses that LDS); d(hidden) below is the same arithmetic either way
+  const bool no_dv = !p.dv_f32 && !p.dv_bf16;
+  if (!no_dv) stage4(0, st0);
+  for (int dc = 0; dc < (((dbg & 4) || no_dv) ? 0 : g.NDC); ++dc) {
     // The gradient rows of this chunk are requested BEFORE the wait for the chunk's Q / dO images: vmcnt is one counter for the DMA,
     // these loads and the stores of the previous chunk, so the wait below drains all three together -- one memory round trip per chunk.
     f32x4 old[2][2][4];
@@ -471,7 +474,7 @@ extern "C" int mart_fusion_fwd(const mart_fusion_fwd_desc* d, void* stream) {
 }
 
 extern "C" int mart_fusion_bwd(const mart_fusion_bwd_desc* d, void* stream) {
-  MART_CHECK(d && d->q && d->v && d->dout && d->probs && d->dq && (d->dv_f32 || d->dv_bf16) && d->B > 0, "fusion_bwd: bad args");
+  MART_CHECK(d && d->q && d->v && d->dout && d->probs && d->dq && d->B > 0, "fusion_bwd: bad args");
   const Plan pl = make_plan(d->Lq, d->Nv, d->H, true);
   MART_CHECK(pl.ok, "fusion_bwd: unsupported shape (mart_fusion_supported)");
   MART_CHECK(d->ldq >= d->H && d->ldv >= d->H && d->lddo >= d->H && d->lddq >= d->H && (!d->dv_f32 || d->lddv >= d->H) && d->ldq % 8 == 0 && d->ldv % 8 == 0 && d->lddo % 8 == 0 &&

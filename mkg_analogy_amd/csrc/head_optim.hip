@@ -184,6 +184,12 @@ __global__ __launch_bounds__(TPB) void adamw_k(mart_adamw_desc p) {
     const int ci = wi / parts, part = wi % parts;
     const int start = p.chunks[3 * ci], len = p.chunks[3 * ci + 1];
     const int flags = p.chunks[3 * ci + 2];
+    if (flags & 4) {                                              // frozen tensor whose gradient a launch still writes: clear it, touch nothing else
+      if (p.zero_grad)
+        for (int base = part * ADAMW_PART; base < len; base += parts * ADAMW_PART)
+          for (int i = base + threadIdx.x, pend = min(len, base + ADAMW_PART); i < pend; i += TPB) p.grad[(long long)start + i] = 0.f;
+      continue;
+    }
     const float wd = (flags & 1) ? p.weight_decay : 0.f;
     const float decay = 1.f - p.lr * wd;
     const float step_size = p.lr / p.bc1;

@@ -482,6 +482,7 @@ __global__ __launch_bounds__(TPB) void text_embed_k(mart_text_embed_desc p) {
 // grid (L positions, batch slices): the word rows are scattered with atomics (ids are arbitrary); the position and
 // token-type rows are summed over the slice in registers first -- one atomic per (slice, position[, type], column)
 // instead of one per token (the two token-type rows used to take 8192 contended adds per column).
+// A NULL dword / dpos / dtype: that table is frozen, its rows are not computed.
 __global__ __launch_bounds__(256) void text_embed_scatter_k(const float* __restrict__ ds, const int64_t* __restrict__ ids, const int64_t* __restrict__ tt,
                                                            float* dword, float* dpos, float* dtype, int B, int L, int H) {
   const int pos = blockIdx.x;
@@ -492,16 +493,16 @@ __global__ __launch_bounds__(256) void text_embed_scatter_k(const float* __restr
     for (int b = b0; b < b1; ++b) {
       const long long m = (long long)b * L + pos;
       const float g = ds[m * H + c];
-      atomicAdd(dword + ids[m] * H + c, g);
+      if (dword) atomicAdd(dword + ids[m] * H + c, g);
       ap += g;
       const long long ty = tt[m];
       if (ty == 0) a0 += g;
       else if (ty == 1) a1 += g;
-      else atomicAdd(dtype + ty * H + c, g);
+      else if (dtype) atomicAdd(dtype + ty * H + c, g);
     }
-    atomicAdd(dpos + (long long)pos * H + c, ap);
-    if (a0 != 0.f) atomicAdd(dtype + c, a0);
-    if (a1 != 0.f) atomicAdd(dtype + H + c, a1);
+    if (dpos) atomicAdd(dpos + (long long)pos * H + c, ap);
+    if (dtype && a0 != 0.f) atomicAdd(dtype + c, a0);
+    if (dtype && a1 != 0.f) atomicAdd(dtype + H + c, a1);
   }
 }
 
@@ -611,7 +612,8 @@ __global__ __launch_bounds__(256) void vision_assemble_reduce_k(const float* __r
   if (c >= H) return;
   float tot = 0.f;
   for (int s = 0; s < nsl; ++s) tot += ws[(((long long)u * nsl + s) * 2) * H + c];                 // first-image row u (u = 0: class token)
-  if (u == 0) dcls[c] += tot;
+  if (u == 0 && dcls) dcls[c] += tot;
+  if (!dpos) return;
   const int t2 = u + tail_shift;                                           // second-image rows whose position row is u
   if (t2 >= 1 && t2 <= P)
     for (int s = 0; s < nsl; ++s) tot += ws[(((long long)t2 * nsl + s) * 2 + 1) * H + c];
@@ -679,7 +681,7 @@ __global__ void vision_assemble_k(const bf16* __restrict__ patch, const float* _
   }
 }
 
-// dpatch = bf16(ds rows 1..2P); dcls += sum_b ds[b,0]; dpos[t] += sum_b (ds[b,t] + ds[b,t+P])
+// dpatch = bf16(ds rows 1..2P); dcls += sum_b ds[b,0]; dpos[t] += sum_b (ds[b,t] + ds[b,t+P]); a NULL dpatch / dcls / dpos is not computed
 // grid (P+1 rows, batch slices), 16-byte accesses; the slice sums reach dcls / dpos with one atomic per (slice, row, column)
 __global__ __launch_bounds__(192) void vision_assemble_bwd_k(const float* __restrict__ ds, bf16* __restrict__ dpatch, float* dcls, float* dpos, int B, int P, int H, int tail_shift, float* ws) {
   const int Nv = 1 + 2 * P;
@@ -694,8 +696,10 @@ __global__ __launch_bounds__(192) void vision_assemble_bwd_k(const float* __rest
       else {
         const f32x4 g0 = *(const f32x4*)(base + (long long)t * H + c), g1 = *(const f32x4*)(base + (long long)(t + P) * H + c);
         acc += g0; acc_tail += g1;
-        *(bf16x4*)(dpatch + ((long long)b * 2 * P + (t - 1)) * H + c) = f4_to_bf4(g0);
-        *(bf16x4*)(dpatch + ((long long)b * 2 * P + (t - 1 + P)) * H + c) = f4_to_bf4(g1);
+        if (dpatch) {
+          *(bf16x4*)(dpatch + ((long long)b * 2 * P + (t - 1)) * H + c) = f4_to_bf4(g0);
+          *(bf16x4*)(dpatch + ((long long)b * 2 * P + (t - 1 + P)) * H + c) = f4_to_bf4(g1);
+        }
       }
     }
     // acc: the first image's row t (position row t); acc_tail: the second image's row t (position row t - tail_shift)
@@ -706,9 +710,9 @@ __global__ __launch_bounds__(192) void vision_assemble_bwd_k(const float* __rest
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      atomicAdd(dpos + (long long)t * H + c + e, acc[e]);
-      if (t > 0) atomicAdd(dpos + (long long)(t - tail_shift) * H + c + e, acc_tail[e]);
-      if (t == 0) atomicAdd(dcls + c + e, acc[e]);
+      if (dpos) atomicAdd(dpos + (long long)t * H + c + e, acc[e]);
+      if (dpos && t > 0) atomicAdd(dpos + (long long)(t - tail_shift) * H + c + e, acc_tail[e]);
+      if (dcls && t == 0) atomicAdd(dcls + c + e, acc[e]);
     }
   }
 }
@@ -925,7 +929,7 @@ extern "C" int mart_text_embed_fwd(const mart_text_embed_desc* d, void* stream) 
 }
 extern "C" int mart_text_embed_scatter(const float* ds, const int64_t* ids, const int64_t* tt, float* dword, float* dpos, float* dtype,
                                        int B, int L, int H, void* stream) {
-  MART_CHECK(ds && ids && tt && dword && dpos && dtype && B > 0 && L > 0 && H > 0, "text_embed_scatter: bad args");
+  MART_CHECK(ds && ids && tt && (dword || dpos || dtype) && B > 0 && L > 0 && H > 0, "text_embed_scatter: bad args");
   hipLaunchKernelGGL(text_embed_scatter_k, dim3(L, B >= 64 ? 16 : 1), dim3(256), 0, (hipStream_t)stream, ds, ids, tt, dword, dpos, dtype, B, L, H);
   MART_LAUNCH_CHECK();
   return 0;
@@ -957,40 +961,49 @@ extern "C" int mart_vision_assemble(const void* patch_bf16, const float* cls, co
   return 0;
 }
 extern "C" int mart_vision_assemble_bwd(const float* ds, void* dpatch_bf16, float* dcls, float* dpos, int B, int P, int H, int tail_shift, void* stream) {
-  MART_CHECK(ds && dpatch_bf16 && dcls && dpos && B > 0 && P > 0 && H > 0 && H % 4 == 0 && (tail_shift == 0 || tail_shift == 1), "vision_assemble_bwd: bad args (H must be a multiple of 4)");
+  MART_CHECK(ds && (dpatch_bf16 || dcls || dpos) && B > 0 && P > 0 && H > 0 && H % 4 == 0 && (tail_shift == 0 || tail_shift == 1), "vision_assemble_bwd: bad args (H must be a multiple of 4)");
   hipLaunchKernelGGL(vision_assemble_bwd_k, dim3(P + 1, B >= 64 ? 16 : 1), dim3(192), 0, (hipStream_t)stream, ds, (bf16*)dpatch_bf16, dcls, dpos, B, P, H, tail_shift, (float*)nullptr);
   MART_LAUNCH_CHECK();
   return 0;
 }
 extern "C" int mart_vision_assemble_bwd_det(const float* ds, void* dpatch_bf16, float* dcls, float* dpos, int B, int P, int H, int tail_shift,
                                             float* ws, long long ws_bytes, void* stream) {
-  MART_CHECK(ds && dpatch_bf16 && dcls && dpos && ws && B > 0 && P > 0 && H > 0 && H % 4 == 0 && (tail_shift == 0 || tail_shift == 1), "vision_assemble_bwd_det: bad args");
+  MART_CHECK(ds && (dpatch_bf16 || dcls || dpos) && ws && B > 0 && P > 0 && H > 0 && H % 4 == 0 && (tail_shift == 0 || tail_shift == 1), "vision_assemble_bwd_det: bad args");
   const int nsl = B >= 64 ? 16 : 1;
   MART_CHECK(ws_bytes >= (long long)(P + 1) * nsl * 2 * H * (long long)sizeof(float), "vision_assemble_bwd_det: workspace too small ((P+1) * 16 * 2 * H floats suffice)");
   hipLaunchKernelGGL(vision_assemble_bwd_k, dim3(P + 1, nsl), dim3(192), 0, (hipStream_t)stream, ds, (bf16*)dpatch_bf16, dcls, dpos, B, P, H, tail_shift, ws);
   MART_LAUNCH_CHECK();
-  hipLaunchKernelGGL(vision_assemble_reduce_k, dim3((H + 255) / 256, P + 1), dim3(256), 0, (hipStream_t)stream, ws, dcls, dpos, P, nsl, H, tail_shift);
-  MART_LAUNCH_CHECK();
+  if (dcls || dpos) {
+    hipLaunchKernelGGL(vision_assemble_reduce_k, dim3((H + 255) / 256, P + 1), dim3(256), 0, (hipStream_t)stream, ws, dcls, dpos, P, nsl, H, tail_shift);
+    MART_LAUNCH_CHECK();
+  }
   return 0;
 }
 extern "C" int mart_text_embed_scatter_det(const float* ds, const int64_t* ids, const int64_t* tt, const int64_t* order, float* dword, float* dpos, float* dtype,
                                            int B, int L, int H, float* ws, long long ws_bytes, int32_t* meta, void* stream) {
-  MART_CHECK(ds && ids && tt && order && dword && dpos && dtype && ws && meta && B > 0 && L > 0 && H > 0, "text_embed_scatter_det: bad args");
+  MART_CHECK(ds && ids && tt && (dword ? order && meta : 1) && (dword || dpos || dtype) && ws && B > 0 && L > 0 && H > 0, "text_embed_scatter_det: bad args");
   const int n = B * L, nwin = (n + ES - 1) / ES, nsl = B >= 64 ? 16 : 1;
   const long long need = ((long long)nwin * 2 + (long long)L * nsl * 2) * H * (long long)sizeof(float);
   MART_CHECK(ws_bytes >= need, "text_embed_scatter_det: workspace too small ((ceil(B*L/64) * 2 + L * 16 * 2) * H floats suffice)");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(embed_word_pass1_k, dim3(nwin), dim3(256), 0, st, ds, ids, order, dword, ws, meta, n, H);
-  MART_LAUNCH_CHECK();
-  hipLaunchKernelGGL(embed_word_pass2_k, dim3(nwin), dim3(256), 0, st, ids, order, dword, ws, meta, n, nwin, H);
-  MART_LAUNCH_CHECK();
+  if (dword) {                                                             // (a frozen table: NULL, its passes are not launched)
+    hipLaunchKernelGGL(embed_word_pass1_k, dim3(nwin), dim3(256), 0, st, ds, ids, order, dword, ws, meta, n, H);
+    MART_LAUNCH_CHECK();
+    hipLaunchKernelGGL(embed_word_pass2_k, dim3(nwin), dim3(256), 0, st, ids, order, dword, ws, meta, n, nwin, H);
+    MART_LAUNCH_CHECK();
+  }
+  if (!dpos && !dtype) return 0;
   float* ws2 = ws + (long long)nwin * 2 * H;
   hipLaunchKernelGGL(embed_postype_partial_k, dim3(L, nsl), dim3(256), 0, st, ds, tt, ws2, B, L, H);
   MART_LAUNCH_CHECK();
-  hipLaunchKernelGGL(embed_postype_reduce_k, dim3((H + 255) / 256, L), dim3(256), 0, st, ws2, dpos, L, nsl, H);
-  MART_LAUNCH_CHECK();
-  hipLaunchKernelGGL(embed_type_reduce_k, dim3((H + 63) / 64), dim3(1024), 0, st, ws2, dtype, L * nsl, H);
-  MART_LAUNCH_CHECK();
+  if (dpos) {
+    hipLaunchKernelGGL(embed_postype_reduce_k, dim3((H + 255) / 256, L), dim3(256), 0, st, ws2, dpos, L, nsl, H);
+    MART_LAUNCH_CHECK();
+  }
+  if (dtype) {
+    hipLaunchKernelGGL(embed_type_reduce_k, dim3((H + 63) / 64), dim3(1024), 0, st, ws2, dtype, L * nsl, H);
+    MART_LAUNCH_CHECK();
+  }
   return 0;
 }
 extern "C" int mart_softmax_fwd(const float* scores, int lds_, void* probs_bf16, int ldp, int R, int C, void* stream) {

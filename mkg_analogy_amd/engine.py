@@ -19,6 +19,7 @@ import os
 import torch
 
 from . import ops
+from .freeze import KEEP_TEXT, KEEP_VISION, Plan, backward_plan
 from .params import FlatStore
 
 BF, F32, HF = torch.bfloat16, torch.float32, torch.float16
@@ -119,6 +120,41 @@ class UnimoEngine:
         # reference golden G7 (emulation on the f32 path, tests/test_parity_full_gpu.py): worst gradient-norm deviation unchanged (7.8e-3 over 431 tensors),
         # worst sampled rel-L2 1.33e-2 -> 1.49e-2 -- the bf16 GEMM operands dominate.  The forward residual streams stay f32.  MART_GRAD_STREAM_BF16=0: f32.
         self.grad_stream_bf16 = os.environ.get("MART_GRAD_STREAM_BF16", "1") == "1"
+        self.plan: Plan = self._plan_for(None)                        # what the backward pass runs (freeze.backward_plan); set_trainable() replaces it
+
+    # ------------------------------------------------------------------ frozen parameters
+    def _plan_for(self, trainable) -> Plan:
+        if trainable is None:
+            dead = tuple(self.st.dead)
+            trainable = [n for n in self.st.slots if not (dead and n.startswith(dead))]
+        return backward_plan(trainable, self.n_layers, self.export_from, self.fuse_from)
+
+    def set_trainable(self, trainable) -> set:
+        """``trainable``: parameter names (``requires_grad`` minus the store's dead tensors; None: all).  Returns the names this engine will write a
+        gradient for (whole launch groups: a frozen member of a partly trainable group is still written and is cleared by its zero-only AdamW chunk)."""
+        self.plan = self._plan_for(trainable)
+        return set(self.plan.written)
+
+    def _g(self, key: str, name: str):
+        """Gradient destination ``name`` when launch group ``key`` runs, else None (the kernels' NULL rule: not computed)."""
+        return self.st.g(name) if self.plan.groups[key] else None
+
+    def _prune(self, sv) -> None:
+        """Rule (c): drop the saved tensors that no launch of the planned backward pass reads.  Called at the END of forward(), when both queues have
+        been joined: a tensor that the other queue still reads must not go back to the allocator of the queue that made it before that."""
+        pl = self.plan
+        if pl.full:
+            return
+        for l in range(self.n_layers):
+            for pre, table in (("t", KEEP_TEXT), ("v", KEEP_VISION)):
+                d = sv[f"{pre}{l}"]
+                for k in table:
+                    if not pl.keeps(pre, l, k):
+                        d[k] = None
+        if not pl.vemb:
+            sv["vemb"] = None
+        if not pl.temb:
+            sv["temb"] = None
 
     # ------------------------------------------------------------------ helpers
     def _lin(self, name):
@@ -550,6 +586,9 @@ class UnimoEngine:
                        out_f32=trans, out_bf16=transb)
             sv["head"] = (xtb, y, zh, hm, hr)
         self._text_done()
+        if keep:
+            sv["fused_all"] = all(sv[f"t{l}"]["fus"] is None or sv[f"t{l}"]["visT"] is None for l in range(self.n_layers))
+            self._prune(sv)
         self._mark("fwd_end")
         if self._tstream is not None:                  # allocated on the text stream, consumed by the caller on the main stream
             trans.record_stream(torch.cuda.current_stream())
@@ -562,6 +601,7 @@ class UnimoEngine:
     def backward(self, sv, dtrans: torch.Tensor) -> None:
         """Accumulates d(loss)/d(param) into FlatStore.grad given d(loss)/d(trans_hidden_states) (f32 [B,L,H])."""
         st, H, nh, I = self.st, self.H, self.nh, self.I
+        pl = self.plan
         dev = dtrans.device
         # the side / text streams fork from this (main) stream: it has to have waited for an off-stream gradient zero-fill / W^T refresh
         # (FlatStore.pending, MART_ASYNC_STEP=1 with zero_grad() between forward and backward) before any of them writes a gradient
@@ -596,23 +636,34 @@ class UnimoEngine:
             Mh = y.shape[0]                                               # B * L, or the B * nr rows the forward pass was asked for
             dtr = dtrans.view(-1, H)                                      # [B * L, H], or compact [B * nr, H] for a row-subset pass
             assert dtr.shape[0] == Mh, "backward: the gradient must have the layout forward() returned (compact for a row-subset pass)"
-            dyb = _e((Mh, H), BF, dev)
-            self._ln_bwd(dy_f32=dtr, s=y, mean=hm, rstd=hr, gamma=st.m(hp + "LayerNorm.weight"), M=Mh, H=H, ds_bf16=dyb,
-                       dgamma=st.g(hp + "LayerNorm.weight"), dbeta=st.g(hp + "LayerNorm.bias"))
-            dzh = _e((Mh, H), BF, dev)
-            ops.act_bwd(dyb, zh, ops.ACT_GELU, dzh)
-            self._wgrad(dzh, xtb, hp + "dense.weight", hp + "dense.bias")
-            d_f32 = _e((Mh, H), F32, dev)                                 # gradient w.r.t. the text stream, f32 part
-            ops.gemm_nt(dzh, st.wt("head"), d_f32)
-            d_b16 = None                                                  # ... plus an optional bf16 part
+            d_f32 = d_b16 = None
+            if pl.head_ln:
+                dyb = _e((Mh, H), BF, dev)
+                self._ln_bwd(dy_f32=dtr, s=y, mean=hm, rstd=hr, gamma=st.m(hp + "LayerNorm.weight"), M=Mh, H=H, ds_bf16=dyb,
+                           dgamma=self._g("head.ln", hp + "LayerNorm.weight"), dbeta=self._g("head.ln", hp + "LayerNorm.bias"))
+            if pl.head_act:
+                dzh = _e((Mh, H), BF, dev)
+                ops.act_bwd(dyb, zh, ops.ACT_GELU, dzh)
+                if pl.g("head.dense"):
+                    self._wgrad(dzh, xtb, hp + "dense.weight", hp + "dense.bias")
+            if pl.head_din:
+                d_f32 = _e((Mh, H), F32, dev)                             # gradient w.r.t. the text stream, f32 part (d_b16: an optional bf16 part)
+                ops.gemm_nt(dzh, st.wt("head"), d_f32)
         if self.grad_ready is not None:
             self._join(); self._text_done(); self._text_begin()
         notify(st.slots["unimo.encoder.text_layer.%d.attention.self.query.weight" % (self.n_layers - 1)].offset)
+        if not pl.head_din:
+            # nothing upstream of the head transform is trainable: the pass ends here (the optimizer / all-reduce consumers still get their last call)
+            self._text_done()
+            self._join()
+            self._mark("bwd_end")
+            notify(st.total)
+            self._pass_end()
+            return
 
         # gradient w.r.t. the vision stream: bf16 only (grad_stream_bf16; needs the fused fusion kernels in every fusion layer and none of the debugging
         # hooks / the side-buffer schedule, which work on the f32 tensor), or f32 + its bf16 copy
-        gb16 = (self.grad_stream_bf16 and self.taps is None and self.inject_grad is None and not self.fusion_side and
-                all(sv[f"t{l}"]["fus"] is None or sv[f"t{l}"]["visT"] is None for l in range(self.n_layers)))
+        gb16 = self.grad_stream_bf16 and self.taps is None and self.inject_grad is None and not self.fusion_side and sv["fused_all"]
         if gb16:
             dxv, dxvb = None, torch.zeros((Mv, H), device=dev, dtype=BF)
         else:
@@ -631,11 +682,16 @@ class UnimoEngine:
 
         def will_side(l):
             t_ = sv.get(f"t{l}") if l >= 0 else None
-            return bool(side_mode and t_ is not None and 0 <= l < self.n_layers - 1 and t_["fus"] is not None and t_["visT"] is None)
+            return bool(side_mode and t_ is not None and 0 <= l < self.n_layers - 1 and l >= self.fuse_from and pl.dvis[l] and t_["visT"] is None)
 
         def text_A(l):
             """Text layer l backward, first part: output LayerNorm, FFN, the fusion op (d(visual) -> dxv in place, or -> a side buffer)."""
             d_f32, d_b16 = T["d_f32"], T["d_b16"]
+            dt = pl.text[l]                                               # how far this block's backward runs (freeze.py)
+            T["A_side"][l] = None
+            if dt < 0:
+                T["A"][l] = None
+                return
             if self.taps is not None and d_f32.shape[0] == Mt:
                 self.taps[f"dtxt{l}"] = (d_f32 + d_b16.float() if d_b16 is not None else d_f32.clone()).view(B, Lq, H)
             if self.inject_grad is not None and f"txt{l}" in self.inject_grad:
@@ -643,22 +699,27 @@ class UnimoEngine:
             with self._text_ctx():
                 t = f"unimo.encoder.text_layer.{l}."
                 s = sv[f"t{l}"]
-                fused = s["fus"] is not None
                 sub = bool(s["sub"])                                      # the post-attention part of this layer ran on the requested rows only
                 Ms = d_f32.shape[0] if sub else Mt
                 ds2, doo = _e((Ms, H), F32, dev), _e((Ms, H), BF, dev)
                 self._ln_bwd(dy_f32=d_f32, dy_bf16=d_b16, s=s["s2"], mean=s["m2"], rstd=s["r2"], gamma=st.m(t + "output.LayerNorm.weight"), M=Ms, H=H,
                            ds_f32=ds2, ds_bf16=doo, p_drop=p_h, seed=seed + 12 + 4 * l,
-                           dgamma=st.g(t + "output.LayerNorm.weight"), dbeta=st.g(t + "output.LayerNorm.bias"))
-                self._wgrad(doo, s["ht"], t + "output.dense.weight", t + "output.dense.bias")
-                dzt = _e((Ms, I), BF, dev)
-                ops.gemm_nt(doo, st.wt(f"t{l}.out"), dzt, mulz=s["zt"], mul_act=ops.ACT_STORED)
-                self._wgrad(dzt, s["ab"], t + "intermediate.dense.weight", t + "intermediate.dense.bias")
-                da2 = _e((Ms, H), BF, dev)
-                ops.gemm_nt(dzt, st.wt(f"t{l}.int"), da2)
-                dctx_fus = side = None
-                if fused:
+                           dgamma=self._g(f"t{l}.out_ln", t + "output.LayerNorm.weight"), dbeta=self._g(f"t{l}.out_ln", t + "output.LayerNorm.bias"))
+                if pl.g(f"t{l}.out"):
+                    self._wgrad(doo, s["ht"], t + "output.dense.weight", t + "output.dense.bias")
+                dzt = da2 = dctx_fus = side = None
+                if dt >= 1:
+                    dzt = _e((Ms, I), BF, dev)
+                    ops.gemm_nt(doo, st.wt(f"t{l}.out"), dzt, mulz=s["zt"], mul_act=ops.ACT_STORED)
+                    if pl.g(f"t{l}.int"):
+                        self._wgrad(dzt, s["ab"], t + "intermediate.dense.weight", t + "intermediate.dense.bias")
+                if dt >= 3:
+                    da2 = _e((Ms, H), BF, dev)
+                    ops.gemm_nt(dzt, st.wt(f"t{l}.int"), da2)
+                if l >= self.fuse_from and dt >= 1 and pl.g(f"t{l}.fus"):
                     self._wgrad(dzt, s["fus"], t + "intermediate.fusion_dense.weight", t + "intermediate.fusion_dense.bias")
+                dvis = pl.dvis[l]                                         # d(visual) of the fusion op: only when something upstream of vision layer l is trainable
+                if l >= self.fuse_from and (dvis or dt >= 4):             # (d(hidden) of the fusion op enters the d(context) GEMM of the second part)
                     if sub:                                                        # d(fusion_output) of the requested rows, zero elsewhere
                         dfr = _e((Ms, H), F32, dev)
                         ops.gemm_nt(dzt, st.wt(f"t{l}.fus"), dfr)
@@ -669,7 +730,9 @@ class UnimoEngine:
                         ops.gemm_nt(dzt, st.wt(f"t{l}.fus"), dfus)
                     if s["visT"] is None:                                          # fused kernel ran forward: its backward twin
                         dctx_fus = _e((Mt, H), BF, dev)
-                        if will_side(l):
+                        if not dvis:
+                            ops.fusion_bwd(s["ctx"], s["visb"], dfus, s["probs"], dctx_fus, None, None, B, Lq, Nv, H)    # NULL d(visual): not computed
+                        elif will_side(l):
                             side = torch.zeros((Mv, H), device=dev, dtype=F32)     # consumed by vision layer l + 1's LayerNorm-1 backward
                             ops.fusion_bwd(s["ctx"], s["visb"], dfus, s["probs"], dctx_fus, side, None, B, Lq, Nv, H)
                         else:
@@ -684,7 +747,9 @@ class UnimoEngine:
                         dctx_fus = _e((Mt, H), BF, dev)
                         ops.gemm_nt(dsc, s["visT"], dctx_fus, M=Lq, N=H, batch=B, stride_a=Lq * Nvp, stride_b=H * Nvp, stride_c=Lq * H)
                         # d(vis) = dS^T ctx + P^T d(fus), accumulated into the vision-stream gradient
-                        if Lq % 64 == 0:
+                        if not dvis:
+                            pass
+                        elif Lq % 64 == 0:
                             # one batched NT product with two K segments and the fp32 accumulate fused as residual: the short
                             # contraction (Lq) makes the transposed-operand form ~2.5x cheaper than two split-1 TN launches with
                             # 65 k atomics per workgroup
@@ -702,13 +767,17 @@ class UnimoEngine:
                             self._text_wait(T["ev_vdone"])
                             ops.gemm_tn(dsc, s["ctx"], dxv, M=Lq, NX=Nv, NY=H, batch=B, stride_x=Lq * Nvp, stride_y=Lq * H, stride_o=Nv * H, splits=1)
                             ops.gemm_tn(s["probs"], dfus, dxv, M=Lq, NX=Nv, NY=H, batch=B, stride_x=Lq * Nvp, stride_y=Lq * H, stride_o=Nv * H, splits=1)
-                    T["ev_tfus"][l] = self._text_record()
+                    if dvis:
+                        T["ev_tfus"][l] = self._text_record()
             T["A"][l] = dict(ds2=ds2, da2=da2, dctx_fus=dctx_fus, Ms=Ms, sub=sub)
             T["A_side"][l] = side
 
         def text_B(l):
             """Second part: attention-output LayerNorm, attention, Q/K/V -> the gradient w.r.t. the layer's input."""
             a = T["A"].pop(l)
+            dt = pl.text[l]
+            if a is None or dt < 3:
+                return
             ds2, da2, dctx_fus, Ms, sub = a["ds2"], a["da2"], a["dctx_fus"], a["Ms"], a["sub"]
             with self._text_ctx():
                 t = f"unimo.encoder.text_layer.{l}."
@@ -716,21 +785,29 @@ class UnimoEngine:
                 ds1, dso = _e((Ms, H), F32, dev), _e((Ms, H), BF, dev)
                 self._ln_bwd(dy_f32=ds2, dy_bf16=da2, s=s["s1"], mean=s["m1"], rstd=s["r1"], gamma=st.m(t + "attention.output.LayerNorm.weight"), M=Ms, H=H,
                            ds_f32=ds1, ds_bf16=dso, p_drop=p_h, seed=seed + 11 + 4 * l,
-                           dgamma=st.g(t + "attention.output.LayerNorm.weight"), dbeta=st.g(t + "attention.output.LayerNorm.bias"))
-                if sub:
+                           dgamma=self._g(f"t{l}.ao_ln", t + "attention.output.LayerNorm.weight"), dbeta=self._g(f"t{l}.ao_ln", t + "attention.output.LayerNorm.bias"))
+                wg_ao = pl.g(f"t{l}.ao")
+                if sub and wg_ao:
                     ctx_r = _e((Ms, H), BF, dev)
                     ops.gather_rows_bf16(s["ctx"], R, ctx_r)
                     self._wgrad(dso, ctx_r, t + "attention.output.dense.weight", t + "attention.output.dense.bias")
+                elif wg_ao:
+                    self._wgrad(dso, s["ctx"], t + "attention.output.dense.weight", t + "attention.output.dense.bias")
+                if dt < 4:
+                    return
+                if sub:
                     dcr = _e((Ms, H), F32, dev)
                     ops.gemm_nt(dso, st.wt(f"t{l}.ao"), dcr)
                     dctx = dctx_fus if dctx_fus is not None else torch.zeros((Mt, H), device=dev, dtype=BF)
                     ops.scatter_rows(dcr, R, nr, dctx, accumulate=True)    # bf16(f32 product + bf16 fusion part): the dense path's one rounding
                 else:
-                    self._wgrad(dso, s["ctx"], t + "attention.output.dense.weight", t + "attention.output.dense.bias")
                     dctx = _e((Mt, H), BF, dev)
                     ops.gemm_nt(dso, st.wt(f"t{l}.ao"), dctx, res_bf16=dctx_fus)
-                # attention backward; for layers whose (K,V) fed a vision layer the k/v blocks already hold the prefix grads
-                has_prefix_grad = self.export_from <= l < self.n_layers - 1
+                if dt < 5:
+                    return
+                # attention backward; for layers whose (K,V) fed a vision layer the k/v blocks already hold the prefix grads (when that layer's
+                # attention backward ran: it left them in s["dqkv"])
+                has_prefix_grad = self.export_from <= l < self.n_layers - 1 and s.get("dqkv") is not None
                 dqkv = s.get("dqkv")
                 if dqkv is None:
                     dqkv = _e((Mt, 3 * H), BF, dev)
@@ -739,10 +816,13 @@ class UnimoEngine:
                 if has_prefix_grad:
                     self._text_wait(T["ev_vattn"])                         # prefix gradients written by vision layer l+1's attention backward
                 ops.attn_bwd(dctx=dctx, delta=delta, dq=dqkv[:, :H], dk=dqkv[:, H:2 * H], dv=dqkv[:, 2 * H:], accum_dkv=has_prefix_grad,
-                             dw=st.g(t + "attention.self.adaptive_weight.0") if sep_on else None, **s["tkw"])
+                             dw=st.g(t + "attention.self.adaptive_weight.0") if sep_on and pl.g(f"t{l}.adaptive") else None, **s["tkw"])
                 names = [t + f"attention.self.{n}" for n in ("query", "key", "value")]
-                gw = st.fused([n + ".weight" for n in names], st.grad)
-                self._tn(dqkv, s["xb"], gw, colsum=st.fused([n + ".bias" for n in names], st.grad))
+                if pl.g(f"t{l}.qkv"):
+                    gw = st.fused([n + ".weight" for n in names], st.grad)
+                    self._tn(dqkv, s["xb"], gw, colsum=st.fused([n + ".bias" for n in names], st.grad))
+                if dt < 6:
+                    return
                 dtb = _e((Mt, H), BF, dev)
                 ops.gemm_nt(dqkv, st.wt(f"t{l}.qkv"), dtb)
                 if sub:                                                    # residual-path gradient of the requested rows into the [B * L, H] stream
@@ -754,6 +834,8 @@ class UnimoEngine:
 
         def text_embed_bwd():
             """Text embeddings backward: dropout -> LN -> scatter into the embedding tables (text stream)."""
+            if not pl.temb:
+                return
             with self._text_ctx():
                 s_t, tmean, trstd = sv["temb"]
                 u = "unimo.text_embeddings."
@@ -761,9 +843,10 @@ class UnimoEngine:
                 ops.dropout_bwd_f32(T["d_f32"], T["d_b16"], dyd, Mt * H, p_h, seed + 1)
                 dse = _e((Mt, H), F32, dev)
                 self._ln_bwd(dy_f32=dyd, s=s_t, mean=tmean, rstd=trstd, gamma=st.m(u + "LayerNorm.weight"), M=Mt, H=H, ds_f32=dse,
-                             dgamma=st.g(u + "LayerNorm.weight"), dbeta=st.g(u + "LayerNorm.bias"))
-                ops.text_embed_scatter(dse, sv["ids"], sv["tt"], st.g(u + "word_embeddings.weight"), st.g(u + "position_embeddings.weight"),
-                                       st.g(u + "token_type_embeddings.weight"), B, Lq, H)
+                             dgamma=self._g("temb.ln", u + "LayerNorm.weight"), dbeta=self._g("temb.ln", u + "LayerNorm.bias"))
+                if pl.g("temb.word") or pl.g("temb.pos") or pl.g("temb.type"):      # a frozen table: NULL, not computed
+                    ops.text_embed_scatter(dse, sv["ids"], sv["tt"], self._g("temb.word", u + "word_embeddings.weight"),
+                                           self._g("temb.pos", u + "position_embeddings.weight"), self._g("temb.type", u + "token_type_embeddings.weight"), B, Lq, H)
 
         T["ev_vdone"], T["ev_vattn"] = ev_vdone, ev_vattn
         text_A(self.n_layers - 1)
@@ -778,7 +861,8 @@ class UnimoEngine:
                     self._join(); self._text_done(); self._text_begin()
                 notify(st.slots["unimo.encoder.vision_layers.0.self_attn.q_proj.weight"].offset)
             side_next = None                                           # d(visual) of the fusion of text layer l - 1, when it travels through a side buffer
-            # ================= vision layer l
+            # ================= vision layer l: runs to depth dv of its chain (freeze.py: 7 = all of it, -1 = nothing)
+            dv = pl.vision[l]
             if l in T["ev_tfus"] and T["A_side"].get(l) is None:
                 self._main_wait(T["ev_tfus"][l])                           # text layer l added d(vis) into dxv in place
             dxvb_fresh = T["fresh"] or T["A_side"].get(l) is not None      # in place: fusion_bwd refreshed the bf16 copy; side buffer: LayerNorm-1 of layer l + 1 did
@@ -786,47 +870,59 @@ class UnimoEngine:
             v = f"unimo.encoder.vision_layers.{l}."
             s = sv[f"v{l}"]
             self._mark(f"bwd_v{l}")
-            if self.taps is not None:
-                self.taps[f"dvis{l}"] = dxv.view(B, Nv, H).clone()
-            if self.inject_grad is not None and f"vis{l}" in self.inject_grad:
-                dxv.copy_(self.inject_grad[f"vis{l}"].reshape(Mv, H))
-                dxvb_fresh = False
-                ops.add_f32_bf16(dxv, None, None, dxvb)
-            elif not gb16 and (l >= self.fuse_from or l == self.n_layers - 1) and not dxvb_fresh:   # fusion of text layer l added d(vis) into dxv
-                ops.add_f32_bf16(dxv, None, None, dxvb)                # -> refresh the bf16 copy (otherwise ln1 bwd wrote it)
-            self._wgrad(dxvb, s["f"], v + "mlp.fc2.weight", v + "mlp.fc2.bias")
-            dz = _e((Mv, I), BF, dev)
-            ops.gemm_nt(dxvb, st.wt(f"v{l}.fc2"), dz, mulz=s["z"], mul_act=ops.ACT_STORED)
-            self._wgrad(dz, s["h2"], v + "mlp.fc1.weight", v + "mlp.fc1.bias")
-            dh2 = _e((Mv, H), BF, dev)
-            ops.gemm_nt(dz, st.wt(f"v{l}.fc1"), dh2)
-            del dz
-            dx1, dx1b = (None if gb16 else _e((Mv, H), F32, dev)), _e((Mv, H), BF, dev)
-            self._ln_bwd(dy_bf16=dh2, s=s["x1"], mean=s["m2"], rstd=s["r2"], gamma=st.m(v + "layer_norm2.weight"), M=Mv, H=H,
-                       add_f32=dxv, add_bf16=dxvb if gb16 else None,
-                       ds_f32=dx1, ds_bf16=dx1b, bf16_total=True, dgamma=st.g(v + "layer_norm2.weight"), dbeta=st.g(v + "layer_norm2.bias"))
-            self._wgrad(dx1b, s["ctx"], v + "self_attn.out_proj.weight", v + "self_attn.out_proj.bias")
-            dctx = dh2                                                 # reuse
-            ops.gemm_nt(dx1b, st.wt(f"v{l}.o"), dctx)
-            dqkv = _e((Mv, 3 * H), BF, dev)
-            delta = _e((B, nh, Nv), F32, dev)
-            pre = s["pre"]
-            dpre = None
-            if pre is not None:                                        # prefix grads land in text layer l-1's dqkv buffer (k,v blocks)
-                dpre = _e((Mt, 3 * H), BF, dev)
-                sv[f"t{l - 1}"]["dqkv"] = dpre
-                self._text_uses(dpre)
-            q = s["qkv"]
-            ops.attn_bwd(dctx=dctx, delta=delta, dq=dqkv[:, :H], dk=dqkv[:, H:2 * H], dv=dqkv[:, 2 * H:],
-                         dpk=dpre[:, H:2 * H] if dpre is not None else None, dpv=dpre[:, 2 * H:] if dpre is not None else None,
-                         q=q[:, :H], k=q[:, H:2 * H], v=q[:, 2 * H:], ctx=s["ctx"], lse=s["lse"], B=B, nh=nh, Sq=Nv, Sk=Nv, scale=0.125,
-                         pk=pre[:, H:2 * H] if pre is not None else None, pv=pre[:, 2 * H:] if pre is not None else None,
-                         Lp=Lq if pre is not None else 0)
-            T["ev_vattn"] = self._main_record()
-            names = [v + f"self_attn.{n}" for n in ("q_proj", "k_proj", "v_proj")]
-            self._tn(dqkv, s["h1"], st.fused([n + ".weight" for n in names], st.grad), colsum=st.fused([n + ".bias" for n in names], st.grad))
-            dh1 = dctx
-            ops.gemm_nt(dqkv, st.wt(f"v{l}.qkv"), dh1)
+            if dv >= 0:
+                if self.taps is not None:
+                    self.taps[f"dvis{l}"] = dxv.view(B, Nv, H).clone()
+                if self.inject_grad is not None and f"vis{l}" in self.inject_grad:
+                    dxv.copy_(self.inject_grad[f"vis{l}"].reshape(Mv, H))
+                    dxvb_fresh = False
+                    ops.add_f32_bf16(dxv, None, None, dxvb)
+                elif not gb16 and (l >= self.fuse_from or l == self.n_layers - 1) and not dxvb_fresh:   # fusion of text layer l added d(vis) into dxv
+                    ops.add_f32_bf16(dxv, None, None, dxvb)                # -> refresh the bf16 copy (otherwise ln1 bwd wrote it)
+                if pl.g(f"v{l}.fc2"):
+                    self._wgrad(dxvb, s["f"], v + "mlp.fc2.weight", v + "mlp.fc2.bias")
+            dh2 = dx1 = dx1b = dctx = dqkv = dh1 = None
+            if dv >= 1:
+                dz = _e((Mv, I), BF, dev)
+                ops.gemm_nt(dxvb, st.wt(f"v{l}.fc2"), dz, mulz=s["z"], mul_act=ops.ACT_STORED)
+                if pl.g(f"v{l}.fc1"):
+                    self._wgrad(dz, s["h2"], v + "mlp.fc1.weight", v + "mlp.fc1.bias")
+                if dv >= 2:
+                    dh2 = _e((Mv, H), BF, dev)
+                    ops.gemm_nt(dz, st.wt(f"v{l}.fc1"), dh2)
+                del dz
+            if dv >= 3:
+                dx1, dx1b = (None if gb16 else _e((Mv, H), F32, dev)), _e((Mv, H), BF, dev)
+                self._ln_bwd(dy_bf16=dh2, s=s["x1"], mean=s["m2"], rstd=s["r2"], gamma=st.m(v + "layer_norm2.weight"), M=Mv, H=H,
+                           add_f32=dxv, add_bf16=dxvb if gb16 else None,
+                           ds_f32=dx1, ds_bf16=dx1b, bf16_total=True, dgamma=self._g(f"v{l}.ln2", v + "layer_norm2.weight"), dbeta=self._g(f"v{l}.ln2", v + "layer_norm2.bias"))
+                if pl.g(f"v{l}.o"):
+                    self._wgrad(dx1b, s["ctx"], v + "self_attn.out_proj.weight", v + "self_attn.out_proj.bias")
+            if dv >= 4:
+                dctx = dh2                                                 # reuse
+                ops.gemm_nt(dx1b, st.wt(f"v{l}.o"), dctx)
+            if dv >= 5:
+                dqkv = _e((Mv, 3 * H), BF, dev)
+                delta = _e((B, nh, Nv), F32, dev)
+                pre = s["pre"]
+                dpre = None
+                if pre is not None:                                        # prefix grads land in text layer l-1's dqkv buffer (k,v blocks)
+                    dpre = _e((Mt, 3 * H), BF, dev)
+                    sv[f"t{l - 1}"]["dqkv"] = dpre
+                    self._text_uses(dpre)
+                q = s["qkv"]
+                ops.attn_bwd(dctx=dctx, delta=delta, dq=dqkv[:, :H], dk=dqkv[:, H:2 * H], dv=dqkv[:, 2 * H:],
+                             dpk=dpre[:, H:2 * H] if dpre is not None else None, dpv=dpre[:, 2 * H:] if dpre is not None else None,
+                             q=q[:, :H], k=q[:, H:2 * H], v=q[:, 2 * H:], ctx=s["ctx"], lse=s["lse"], B=B, nh=nh, Sq=Nv, Sk=Nv, scale=0.125,
+                             pk=pre[:, H:2 * H] if pre is not None else None, pv=pre[:, 2 * H:] if pre is not None else None,
+                             Lp=Lq if pre is not None else 0)
+                T["ev_vattn"] = self._main_record()
+                if pl.g(f"v{l}.qkv"):
+                    names = [v + f"self_attn.{n}" for n in ("q_proj", "k_proj", "v_proj")]
+                    self._tn(dqkv, s["h1"], st.fused([n + ".weight" for n in names], st.grad), colsum=st.fused([n + ".bias" for n in names], st.grad))
+            if dv >= 6:
+                dh1 = dctx
+                ops.gemm_nt(dqkv, st.wt(f"v{l}.qkv"), dh1)
             del dqkv
             early = will_side(l - 1)
             if early:
@@ -836,17 +932,18 @@ class UnimoEngine:
                 side_next = T["A_side"][l - 1]
                 self._main_wait(T["ev_tfus"][l - 1])
                 side_next.record_stream(torch.cuda.current_stream())   # allocated on the text stream, read here
-            if self.wgrad_lag and self.overlap_wgrad:
-                # a fresh bf16 buffer for the gradient this LayerNorm writes instead of a join: the fc2 weight-gradient GEMM of this layer may still
-                # be reading the old one on the weight-gradient stream (the caching allocator keeps it until that stream has passed it: record_stream
-                # in _tn), and the main queue goes on while the weight-gradient queue lags behind by more than one layer
-                dxvb = _e((Mv, H), BF, dev)
-            else:
-                self._join()                                           # dxvb (read by the fc2 weight-gradient GEMM) is rewritten next
-            self._ln_bwd(dy_bf16=dh1, s=s["x"], mean=s["m1"], rstd=s["r1"], gamma=st.m(v + "layer_norm1.weight"), M=Mv, H=H, add_f32=dx1,
-                       add_bf16=dx1b if gb16 else None, add2_f32=side_next, ds_f32=dxv, ds_bf16=dxvb, bf16_total=True,
-                       dgamma=st.g(v + "layer_norm1.weight"), dbeta=st.g(v + "layer_norm1.bias"))
-            T["dxvb"] = dxvb                                           # (a fresh buffer under wgrad_lag: what text layer l - 1's fusion backward updates)
+            if dv >= 7:
+                if self.wgrad_lag and self.overlap_wgrad:
+                    # a fresh bf16 buffer for the gradient this LayerNorm writes instead of a join: the fc2 weight-gradient GEMM of this layer may still
+                    # be reading the old one on the weight-gradient stream (the caching allocator keeps it until that stream has passed it: record_stream
+                    # in _tn), and the main queue goes on while the weight-gradient queue lags behind by more than one layer
+                    dxvb = _e((Mv, H), BF, dev)
+                else:
+                    self._join()                                           # dxvb (read by the fc2 weight-gradient GEMM) is rewritten next
+                self._ln_bwd(dy_bf16=dh1, s=s["x"], mean=s["m1"], rstd=s["r1"], gamma=st.m(v + "layer_norm1.weight"), M=Mv, H=H, add_f32=dx1,
+                           add_bf16=dx1b if gb16 else None, add2_f32=side_next, ds_f32=dxv, ds_bf16=dxvb, bf16_total=True,
+                           dgamma=self._g(f"v{l}.ln1", v + "layer_norm1.weight"), dbeta=self._g(f"v{l}.ln1", v + "layer_norm1.bias"))
+                T["dxvb"] = dxvb                                           # (a fresh buffer under wgrad_lag: what text layer l - 1's fusion backward updates)
             if early:
                 T["A_side"][l - 1] = True                              # consumed: keep the "a side buffer existed" mark, drop the [Mv, H] f32 tensor
                 del side_next
@@ -861,15 +958,19 @@ class UnimoEngine:
                 notify(st.slots[f"unimo.encoder.text_layer.{l - 1}.attention.self.query.weight"].offset)
 
         # ---- vision embeddings backward: pre-LN -> assemble -> patch GEMM weight gradient
-        patches, s_v, vmean, vrstd = sv["vemb"]
-        dsv = _e((Mv, H), F32, dev)
-        self._ln_bwd(dy_f32=dxv, dy_bf16=dxvb if gb16 else None, s=s_v, mean=vmean, rstd=vrstd, gamma=st.m("unimo.vision_pre_layrnorm.weight"), M=Mv, H=H, ds_f32=dsv,
-                   dgamma=st.g("unimo.vision_pre_layrnorm.weight"), dbeta=st.g("unimo.vision_pre_layrnorm.bias"))
-        dpe = _e((B * 2 * P, H), BF, dev)
-        ops.vision_assemble_bwd(dsv, dpe, st.g("unimo.vision_embeddings.class_embedding"), st.g("unimo.vision_embeddings.position_embedding.weight"),
-                                B, P, H)
-        gw = st.g("unimo.vision_embeddings.patch_embedding.weight")
-        self._tn(dpe, patches, gw.view(H, -1))
+        if pl.vemb:
+            patches, s_v, vmean, vrstd = sv["vemb"]
+            dsv = _e((Mv, H), F32, dev)
+            self._ln_bwd(dy_f32=dxv, dy_bf16=dxvb if gb16 else None, s=s_v, mean=vmean, rstd=vrstd, gamma=st.m("unimo.vision_pre_layrnorm.weight"), M=Mv, H=H, ds_f32=dsv,
+                       dgamma=self._g("vemb.ln", "unimo.vision_pre_layrnorm.weight"), dbeta=self._g("vemb.ln", "unimo.vision_pre_layrnorm.bias"))
+            wg_patch = pl.g("vemb.patch")
+            if wg_patch or pl.g("vemb.cls") or pl.g("vemb.pos"):
+                dpe = _e((B * 2 * P, H), BF, dev) if wg_patch else None    # a frozen tensor: NULL, not computed
+                ops.vision_assemble_bwd(dsv, dpe, self._g("vemb.cls", "unimo.vision_embeddings.class_embedding"),
+                                        self._g("vemb.pos", "unimo.vision_embeddings.position_embedding.weight"), B, P, H)
+                if wg_patch:
+                    gw = st.g("unimo.vision_embeddings.patch_embedding.weight")
+                    self._tn(dpe, patches, gw.view(H, -1))
         self._mark("bwd_embed_end")
         self._text_done()                                             # main stream waits for the text stream
         self._join()

@@ -152,7 +152,17 @@ class _ScoreFn(torch.autograd.Function):
         ops.scatter_add_rows_f32(drows, rows, dtrans.view(-1, H))
         trows = torch.empty((R, H), device=dev, dtype=BF)
         ops.gather_rows_bf16(transb, rows, trows)
-        ops.gemm_tn(dl, trows, store.g(word_name), NX=A, out_rows=ids, colsum=store.g(bias_name), colsum_by_row=True)
+        # frozen parameters (FlatStore.set_trainable): a frozen bias gets no column sums, a frozen word table no row scatter
+        wg_word, wg_bias = store.writes_grad(word_name), store.writes_grad(bias_name)
+        if wg_word:
+            ops.gemm_tn(dl, trows, store.g(word_name), NX=A, out_rows=ids, colsum=store.g(bias_name) if wg_bias else None, colsum_by_row=True)
+        elif wg_bias:
+            # the bias gradient is the column sum that rides on the row-gradient GEMM: the same launch (the same summation order, so the bias
+            # gradient is bit-identical to the unfrozen pass's) with its [A, H] product sent to a scratch tile instead of the frozen table's rows
+            scratch = torch.zeros((A, H), device=dev, dtype=F32)
+            db = torch.zeros(A, device=dev, dtype=F32)
+            ops.gemm_tn(dl, trows, scratch, NX=A, colsum=db)
+            ops.scatter_add_rows_f32(db.view(A, 1), ids, store.g(bias_name).view(-1, 1))
         return dtrans, None, None, None, None, None, None, None
 
 

@@ -194,8 +194,10 @@ class TransformerLitModel(BaseLitModel):
     # -- lit_models/transformer.py:224-241
     def configure_optimizers(self):
         dead = [n for n in self.model.store.slots if "adaptive_weight" in n] if self.args.pretrain else []
-        if self.args.pretrain:          # no sep_idx => the adaptive weights get grad None in the reference => torch never touches them
-            self.model.store.rebuild_chunks(extra_dead=dead)
+        # the trainable set is read HERE, once: requires_grad (the reference filters on it, transformer.py:228-229) minus the tensors that never get a
+        # gradient (pretrain: no sep_idx => the adaptive weights get grad None in the reference => torch never touches them)
+        if hasattr(self.model, "sync_trainable"):
+            self.model.sync_trainable(extra_dead=dead)
         if self.optimizer_name == "AdamW":
             optimizer = FusedAdamW(self.model, lr=self.lr, eps=1e-8, weight_decay=self.args.weight_decay)
         else:                           # base.py:31: any torch.optim class by name (torch's own update on the fp32 master views; not the fused path)
@@ -204,10 +206,20 @@ class TransformerLitModel(BaseLitModel):
         scheduler = LinearWarmupSchedule(optimizer, num_warmup_steps=steps * self.args.warm_up_radio, num_training_steps=steps)
         return {"optimizer": optimizer, "lr_scheduler": {"scheduler": scheduler, "interval": "step", "frequency": 1}}
 
-    def _freeze_attention(self):
-        raise NotImplementedError("parameter freezing is commented out in the reference (transformer.py:36-39) and unsupported here")
+    # -- the reference's two freezing hooks (lit_models/transformer.py:243-254), by their substring rule.  Flags only: call them before
+    # configure_optimizers(), which reads the flags (HipMaskedLM.sync_trainable); a later change is refused at the next training forward pass.
+    def _set_word_rule(self, keep_word: bool):
+        for name, p in self.model.named_parameters():
+            if ("word" in name) != keep_word:
+                p.requires_grad_(False)
 
-    _freeze_word_embedding = _freeze_attention
+    def _freeze_attention(self):
+        """Only the parameters whose name contains "word" (the tied word embedding) stay trainable."""
+        self._set_word_rule(keep_word=True)
+
+    def _freeze_word_embedding(self):
+        """The parameters whose name contains "word" are frozen; everything else keeps its flag."""
+        self._set_word_rule(keep_word=False)
 
     @staticmethod
     def add_to_argparse(parser):

@@ -53,6 +53,8 @@ class HipMaskedLM(nn.Module):
         self.base_seed = 0x5EED                     # dropout stream; distributed.GradSync hashes the rank into it
         self.precision = "bf16"
         self.image_table = None                     # optional resident [N_img, 3, S, S] f32 table for device-side batch assembly
+        self._flags = None                          # requires_grad of every parameter as sync_trainable() last read it (name, flag) -- the plan in use
+        self._extra_dead: tuple = ()
 
     def _tie_and_hook(self):
         """Last line of a subclass constructor, once the parameter containers exist."""
@@ -134,7 +136,78 @@ class HipMaskedLM(nn.Module):
         self._engine = self._make_engine(self._store)
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
         self._store.bind(self)
+        self._flags = None
+        self.sync_trainable(self._extra_dead)         # a new store starts from the flags as they are now
         return self._store
+
+    # ------------------------------------------------------------------ frozen parameters
+    # ONE rule for "what is trainable": requires_grad = True minus the store's dead tensors, read at ONE moment -- sync_trainable(), which
+    # lit_models' configure_optimizers() calls before it builds the optimizer.  The store (AdamW chunk table) and the engine (backward schedule) are
+    # told together; a flag that moves afterwards is refused at the next training forward pass instead of being half honoured.
+    def _select(self, prefixes):
+        named = list(self.named_parameters())
+        if not prefixes:
+            return [p for _, p in named]
+        hit = [p for n, p in named if n.startswith(tuple(prefixes))]
+        if not hit:
+            raise ValueError(f"no parameter name starts with any of {list(prefixes)}")
+        return hit
+
+    def freeze(self, *name_prefixes: str):
+        """``requires_grad_(False)`` on every parameter whose name starts with one of the prefixes (none given: all).  Flags only: call
+        ``sync_trainable()`` (or the lit model's ``configure_optimizers()``) afterwards."""
+        for p in self._select(name_prefixes):
+            p.requires_grad_(False)
+        return self
+
+    def unfreeze(self, *name_prefixes: str):
+        for p in self._select(name_prefixes):
+            p.requires_grad_(True)
+        return self
+
+    def _read_flags(self):
+        return tuple((n, bool(p.requires_grad)) for n, p in self.named_parameters())
+
+    def sync_trainable(self, extra_dead=()):
+        """Read ``requires_grad`` of every parameter NOW and hand the trainable set to the store and the engine: frozen tensors get no AdamW update
+        (no weight decay, untouched m / v / master / shadows), the MKGformer bf16 engine drops the backward launches nobody consumes
+        (mkg_analogy_amd/freeze.py), and whatever an engine still writes for a frozen tensor is cleared with the step.  ``extra_dead``: run-mode
+        specific tensors that never receive a gradient (FlatStore.rebuild_chunks).  When the set changes the gradient buffer is zero-filled once.
+        Returns the trainable names."""
+        st = self.finalize()
+        flags = self._read_flags()
+        changed = self._flags is not None and (flags != self._flags or tuple(extra_dead) != self._extra_dead)    # (None: a new store, all-zero already)
+        self._flags, self._extra_dead = flags, tuple(extra_dead)
+        self._plist = [p for _, p in self.named_parameters()]
+        self._fingerprint = tuple(f for _, f in flags)
+        self._apply_trainable()
+        if changed:
+            st.zero_grad()
+        return st.trainable_names()
+
+    def _apply_trainable(self):
+        """Store + engine follow ``self._flags`` (the engine that the current precision runs decides which frozen tensors are still written)."""
+        st = self._store
+        frozen = frozenset(n for n, f in self._flags if not f)
+        st.rebuild_chunks(self._extra_dead, frozen=frozen)
+        written = None
+        if hasattr(self._engine, "set_trainable"):
+            written = self._engine.set_trainable(st.trainable_names())
+            if self.precision != "bf16":
+                written = None                         # the fp32 engines run every launch (tier 2: the optimizer alone honours the flags)
+        st.rebuild_chunks(self._extra_dead, written=written)
+        # nothing trainable at all: the output needs no gradient, and loss.backward() fails as torch does for such an output
+        self._anchor.requires_grad_(bool(st.trainable_names()))
+
+    def _check_trainable(self):
+        """First thing in a training forward pass under grad: the flags must be the ones the plan in use was made from."""
+        if not (self.training and torch.is_grad_enabled()) or self._flags is None:
+            return
+        if tuple(p.requires_grad for p in self._plist) == self._fingerprint:      # ~450 attribute reads; no walk of the module tree
+            return
+        n = next(n for (n, f), p in zip(self._flags, self._plist) if f != bool(p.requires_grad))
+        raise RuntimeError(f"requires_grad of '{n}' changed after the trainable set was read: call configure_optimizers() / "
+                           f"model.sync_trainable() again (the optimizer and the backward schedule still follow the old set)")
 
     @property
     def store(self) -> FlatStore:
@@ -167,7 +240,9 @@ class HipMaskedLM(nn.Module):
         gradients are enabled, ViLT and VisualBERT refuse that."""
         if precision not in ("bf16", "fp32"):
             raise ValueError("precision must be 'bf16' or 'fp32'")
-        self.precision = precision
+        changed, self.precision = precision != self.precision, precision
+        if changed and self._store is not None and self._flags is not None and not all(f for _, f in self._flags):
+            self._apply_trainable()                    # which frozen tensors are still written depends on the engine that runs
         return self
 
     def set_image_table(self, table: torch.Tensor):

@@ -191,6 +191,7 @@ class FlavaForMaskedLM(HipMaskedLM):
         if bool_masked_pos is not None or position_ids is not None or image_attention_mask is not None or skip_multimodal_encoder or output_attentions:
             raise NotImplementedError("MarT never passes these FlavaForMaskedLM arguments; unsupported on the HIP path")
         st = self.finalize()
+        self._check_trainable()
         dev = st.device
         input_ids, attention_mask, token_type_ids, sep_idx = self._text_inputs(dev, input_ids, attention_mask, token_type_ids, sep_idx)
         pixel_values = pixel_values.to(dev, torch.float32)

@@ -207,6 +207,7 @@ class UnimoForMaskedLM(HipMaskedLM):
         if position_ids is not None or head_mask is not None:
             raise NotImplementedError("position_ids / head_mask are unused by MarT (modeling_unimo.py:78-80) and unsupported here")
         st = self.finalize()
+        self._check_trainable()
         dev = st.device
         input_ids, attention_mask, token_type_ids, sep_idx = self._text_inputs(dev, input_ids, attention_mask, token_type_ids, sep_idx)
         B, L = input_ids.shape

@@ -146,6 +146,7 @@ class ViltForMaskedLM(HipMaskedLM):
         if fp32 and labels is not None:
             raise NotImplementedError("precision='fp32': no full-vocabulary labels path; score slices of .logits instead")
         st = self.finalize()
+        self._check_trainable()
         dev = st.device
         input_ids, attention_mask, token_type_ids, sep_idx = self._text_inputs(dev, input_ids, attention_mask, token_type_ids, sep_idx)
         pixel_values, image_table, image_index = self._image_inputs(dev, pixel_values, image_index)

@@ -132,6 +132,7 @@ class VisualBertForMaskedLM(HipMaskedLM):
         if fp32 and labels is not None:
             raise NotImplementedError("precision='fp32': no full-vocabulary labels path; score slices of .logits instead")
         st = self.finalize()
+        self._check_trainable()
         dev = st.device
         input_ids, attention_mask, token_type_ids, sep_idx = self._text_inputs(dev, input_ids, attention_mask, token_type_ids, sep_idx)
         pixel_values = pixel_values.to(dev, torch.float32).contiguous()

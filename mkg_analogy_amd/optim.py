@@ -15,15 +15,20 @@ class FusedAdamW(torch.optim.Optimizer):
 
     ``param_groups`` mirrors the reference's two groups (decay 0.01 / 0 by the substring rule) for inspection and
     for the scheduler's ``lr`` plumbing; tensors that never receive a gradient in the reference (dead pooler /
-    post-layernorm: grad None => torch skips them entirely) are left untouched.
+    post-layernorm: grad None => torch skips them entirely) and frozen tensors (``requires_grad = False`` when
+    ``model.sync_trainable()`` / ``configure_optimizers()`` read the flags) are left untouched: no update, no weight
+    decay, and their m / v / master / shadows never change.
     """
 
     def __init__(self, model, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, grad_scale: float = 1.0):
         self.model = model
         store = model.store
+        # the groups name exactly the tensors the chunk table updates: the trainable set the store was last handed (HipMaskedLM.sync_trainable --
+        # requires_grad minus the dead tensors, read once), not a second reading of the flags
         named = dict(model.named_parameters())
-        decay = [p for n, p in named.items() if p.requires_grad and not any(nd in n for nd in NO_DECAY)]
-        no_decay = [p for n, p in named.items() if p.requires_grad and any(nd in n for nd in NO_DECAY)]
+        names = store.trainable_names()
+        decay = [named[n] for n in names if not any(nd in n for nd in NO_DECAY)]
+        no_decay = [named[n] for n in names if any(nd in n for nd in NO_DECAY)]
         groups = [{"params": decay, "weight_decay": weight_decay}, {"params": no_decay, "weight_decay": 0}]
         super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.m = torch.zeros_like(store.master)
@@ -167,7 +172,8 @@ class TorchOptimizerOnStore:
         cls = getattr(torch.optim, name)                       # AttributeError for an unknown name, as the reference
         store = model.store
         dead = tuple(store.dead) + tuple(extra_dead)
-        named = {n: p for n, p in model.named_parameters() if p.requires_grad and not (dead and n.startswith(dead))}
+        every = dict(model.named_parameters())
+        named = {n: every[n] for n in store.trainable_names() if not (dead and n.startswith(dead))}     # the set FusedAdamW's chunk table uses
         decay = [p for n, p in named.items() if not any(nd in n for nd in NO_DECAY)]
         no_decay = [p for n, p in named.items() if any(nd in n for nd in NO_DECAY)]
         self.inner = cls([{"params": decay, "weight_decay": weight_decay}, {"params": no_decay, "weight_decay": 0}], lr=lr, eps=eps)

@@ -132,6 +132,42 @@ def gemm_weight_names(n_layers: int) -> List[Tuple[str, Tuple[str, ...]]]:
     return g
 
 
+ZERO_ONLY = 4                                     # chunk flag bit 2: write 0 to the gradient elements, touch nothing else (include/mart_hip.h)
+
+
+def chunk_table(order, slots, dead=(), frozen=frozenset(), written=None, f16_weight=None, chunk: int = 1 << 16) -> List[List[int]]:
+    """[start, length, flags] of every AdamW chunk, in layout order (pure host logic).  flags: bit 0 weight decay, bit 1 fp16 shadow, bit 2
+    (``ZERO_ONLY``) a frozen tensor whose gradient is still written.  Dead tensors and frozen tensors nobody writes have no chunk."""
+    out: List[List[int]] = []
+    dead = tuple(dead)
+
+    def flags_of(name):
+        if dead and name.startswith(dead):
+            return None
+        if name in frozen:
+            return ZERO_ONLY if (written is None or name in written) else None
+        f = 0 if any(nd in name for nd in NO_DECAY) else 1
+        if f16_weight is not None and f16_weight(name):
+            f |= 2                                             # flag bit 1: AdamW refreshes the fp16 shadow of this chunk too
+        return f
+
+    for name in order:
+        if name.endswith(PACK_WITH_PREV):
+            continue
+        s = slots[name]
+        f = flags_of(name)
+        spans = [(s.offset, s.numel, f)]
+        if name.endswith("adaptive_weight.0"):                 # adaptive_weight.1 shares the slot: one chunk of two elements unless only one of them is frozen
+            f1 = flags_of(name[:-1] + "1")
+            spans = [(s.offset, s.numel + 1, f)] if f1 == f else [(s.offset, s.numel, f), (s.offset + s.numel, 1, f1)]
+        for off, n, fl in spans:
+            if fl is None:
+                continue
+            for c0 in range(0, n, chunk):
+                out.append([off + c0, min(chunk, n - c0), fl])
+    return out
+
+
 class FlatStore:
     def __init__(self, named_params: Dict[str, torch.nn.Parameter], n_layers: int, device: torch.device,
                  order: Optional[List[str]] = None, gemm_groups=None, dead: Sequence[str] = DEAD, f16_weight=text_f16_weight):
@@ -189,33 +225,44 @@ class FlatStore:
         self.ttable = torch.tensor(table, dtype=torch.int64, device=device)
         # AdamW chunk table: (start, len, decay_flag); dead tensors are excluded (grad None in the reference => untouched)
         self.order = order
+        self.frozen = frozenset()                                  # names with requires_grad = False (HipMaskedLM.sync_trainable)
         self.version = 0                                           # bumped whenever the master weights change (derived operand caches)
         self.mark_grad_clean()                                     # the gradient buffer is all-zero (FusedAdamW.fused_zero_grad / zero_grad)
         self.rebuild_chunks()
         self.refresh_shadows()
 
-    def rebuild_chunks(self, extra_dead: Sequence[str] = ()) -> None:
-        """AdamW chunk table.  Tensors that never receive a gradient in the reference (grad None => torch.optim skips them:
-        no update, no weight decay) are left out; ``extra_dead`` adds run-mode specific ones (e.g. adaptive weights when
-        pre-training without sep_idx)."""
-        device = self.device
-        chunks = []
-        CH = 1 << 16
-        dead = tuple(self.dead) + tuple(extra_dead)
-        for name in self.order:
-            if name.endswith(PACK_WITH_PREV):
-                continue
-            if dead and name.startswith(dead):
-                continue
-            s = self.slots[name]
-            n = s.numel + (1 if name.endswith("adaptive_weight.0") else 0)
-            decay = 0 if any(nd in name for nd in NO_DECAY) else 1
-            if self.f16_weight is not None and self.f16_weight(name):
-                decay |= 2                                     # flag bit 1: AdamW refreshes the fp16 shadow of this chunk too
-            for c0 in range(0, n, CH):
-                chunks.append([s.offset + c0, min(CH, n - c0), decay])
-        self.chunks = torch.tensor(chunks, dtype=torch.int32, device=device)
-        self.n_chunks = len(chunks)
+    def rebuild_chunks(self, extra_dead: Sequence[str] = (), frozen=None, written=None) -> None:
+        """AdamW chunk table (:func:`chunk_table`).  Tensors that never receive a gradient in the reference (grad None => torch.optim skips them:
+        no update, no weight decay) are left out; ``extra_dead`` adds run-mode specific ones (e.g. adaptive weights when pre-training without
+        sep_idx).  ``frozen`` (names with ``requires_grad = False``; None: keep the current set) get no update chunk either -- torch's behaviour
+        for ``grad is None``: no Adam update, no weight decay, m / v / master / shadows untouched.  ``written`` (None: every tensor) names the
+        tensors the engine in use writes a gradient for: a frozen one among them (an engine without schedule skipping, or the frozen member of a
+        partly trainable launch group) gets a zero-only chunk, so the gradient buffer is still all-zero after a stepping ``train_step``."""
+        if frozen is not None:
+            self.frozen = frozenset(frozen)
+        self.extra_dead = tuple(extra_dead)
+        self.written = None if written is None else frozenset(written)
+        key = (self.extra_dead, self.frozen, self.written)         # (switching the evaluation precision swaps between two tables per batch)
+        cache = self.__dict__.setdefault("_chunk_cache", {})
+        if key not in cache:
+            chunks = chunk_table(self.order, self.slots, tuple(self.dead) + self.extra_dead, self.frozen, self.written, self.f16_weight)
+            if len(cache) > 8:
+                cache.clear()
+            cache[key] = torch.tensor(chunks, dtype=torch.int32, device=self.device).view(-1, 3)
+        self.chunks = cache[key]
+        self.n_chunks = int(self.chunks.shape[0])
+
+    def is_dead(self, name: str) -> bool:
+        dead = tuple(self.dead) + tuple(getattr(self, "extra_dead", ()))
+        return bool(dead) and name.startswith(dead)
+
+    def trainable_names(self) -> List[str]:
+        """The one rule: ``requires_grad`` (as last read by ``sync_trainable``) minus the dead tensors, in layout order."""
+        return [n for n in self.order if n not in self.frozen and not self.is_dead(n)]
+
+    def writes_grad(self, name: str) -> bool:
+        """Does the engine in use write a gradient for ``name``?  (Frozen tensors of launch groups that still run included.)"""
+        return name not in self.frozen or self.written is None or name in self.written
 
     # ------------------------------------------------------------------ views
     def m(self, name: str) -> torch.Tensor:
