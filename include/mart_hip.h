@@ -347,6 +347,14 @@ int mart_lsce_bwd(const float* logits, int ld, const int64_t* label, long long i
 /* rank = 1 + #(logit > logit[label])  == argsort(argsort(-logits))[label]+1 without ties (lit_models/transformer.py:162-164);
  * a label outside [0, C) gives rank 0 */
 int mart_rank(const float* logits, int ld, const int64_t* label, int64_t* rank, int R, int C, void* stream);
+/* The k best columns of every row: values[r, :] / indices[r, :] are the first k columns of torch.sort(row r, descending=True, stable=True),
+ * row r being logits[r*ld .. r*ld + C).  Needs ld >= C (any ld: rows need no alignment), 1 <= k <= 64, k <= C, R >= 1; anything else is refused.
+ * The order is total: values descend, equal values come in ascending index order.  -0.0 and +0.0 are equal (index order decides); +inf and -inf
+ * are ordinary values; every NaN sorts before +inf and NaNs are equal among themselves (a poisoned row -- one outside a needed_rows promise --
+ * shows up at the top instead of hiding); denormals and floats that differ in the last mantissa bit keep their order: the selection works on an
+ * order-preserving integer image of the float, never on float arithmetic or buckets.  values holds the row's own bits (-0.0 stays -0.0).
+ * Bit-identical from run to run: LDS integer counters only, no float atomics, plain vector stores for both outputs. */
+int mart_topk(const float* logits, int ld, int R, int C, int k, float* values /* [R,k] */, int32_t* indices /* [R,k] */, void* stream);
 /* relaxation loss rows (lit_models/transformer.py:103-108): relu(cos(q,a)) + 1 - cos(r0,r1) on rows of trans.
  * rows == NULL: trans is the dense [B,L,H] tensor.  rows != NULL (row-subset pass): trans is the COMPACT [B*nr, H] tensor and rows[b*nr + j] the flat id
  * b*L + position of its slot j; a position the pass was not promised makes that example's loss NaN (nothing is read for it). */

@@ -149,6 +149,7 @@ _SIGS = {
     "mart_lsce_fwd": (i32, [vp, i32, vp, i64, f32, vp, vp, vp, i32, vp, i32, i32, vp]),
     "mart_lsce_bwd": (i32, [vp, i32, vp, i64, vp, f32, vp, i32, f32, vp, vp, i32, vp, i32, i32, vp]),
     "mart_rank": (i32, [vp, i32, vp, vp, i32, i32, vp]),
+    "mart_topk": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
     "mart_simloss_fwd": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
     "mart_simloss_bwd": (i32, [vp, vp, vp, vp, vp, i32, vp, f32, vp, i32, i32, i32, vp]),
     "mart_needed_rows": (i32, [vp, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp]),

@@ -107,6 +107,102 @@ __global__ void rank_k(const float* __restrict__ lg, int ld, const int64_t* __re
   if (threadIdx.x == 0) rank[r] = (int64_t)(cnt + 0.5f) + 1;
 }
 
+// ---- top-k of every row in the order of torch.sort(row, descending=True, stable=True) (contract: include/mart_hip.h, mart_topk)
+// Order-preserving integer image of a float, integer arithmetic only (no denormal mode can touch it): a larger key is an earlier place.
+// Every NaN -> the largest key (before +inf), -0.0 -> the key of +0.0 (index order decides between them).
+__device__ __forceinline__ uint32_t topk_key(uint32_t u) {
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+  if ((u << 1) == 0u) return 0x80000000u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+constexpr int TOPK_MAX = 64, TOPK_ITEMS = 4;
+// One workgroup per row.  (1) Radix select, four 8-bit digits from the top: the key T of place k, G = #(key > T) < k, need = k - G members of T's tie
+// class.  The LDS histogram counters are integer atomics: their totals do not depend on arrival order.  (2) One ordered pass: thread t owns
+// TOPK_ITEMS consecutive columns of each 1024-column chunk, a packed prefix sum over the workgroup gives every key > T and every key == T its
+// position IN INDEX ORDER -- the first `need` members of the tie class are taken, whichever thread reaches them first (the class can be the whole
+// row: the pass stops at the chunk that completes the list).  (3) The k candidates are placed by (key descending, index ascending) rank.
+// The row (168 KB at C = 42 007: more than LDS) is re-read from L2 by every pass; any ld / alignment: 4-byte loads only.
+__global__ __launch_bounds__(TPB) void topk_k(const float* __restrict__ lg, int ld, int C, int k, float* __restrict__ values, int32_t* __restrict__ indices) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t sel[2];
+  __shared__ uint32_t wtot[2][TPB / 64];
+  __shared__ uint32_t ckey[TOPK_MAX];
+  __shared__ int cidx[TOPK_MAX];
+  const int r = blockIdx.x, t = threadIdx.x;
+  const uint32_t* x = reinterpret_cast<const uint32_t*>(lg + (long long)r * ld);
+  uint32_t prefix = 0, kr = (uint32_t)k;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    hist[t] = 0;
+    __syncthreads();
+    const uint32_t himask = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
+    for (uint32_t c = t; c < (uint32_t)C; c += TPB) {                 // (unsigned: c + TPB cannot wrap for any int C)
+      const uint32_t key = topk_key(x[c]);
+      if ((key & himask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    uint32_t above = 0;
+    for (int b = t + 1; b < 256; ++b) above += hist[b];
+    if (above < kr && kr <= above + hist[t]) { sel[0] = (uint32_t)t; sel[1] = kr - above; }     // exactly one digit holds place kr
+    __syncthreads();
+    prefix |= sel[0] << shift;
+    kr = sel[1];
+  }
+  const uint32_t T = prefix, need = kr, G = (uint32_t)k - need;
+  const int lane = t & 63, w = t >> 6;
+  uint32_t gtot = 0, etot = 0;
+  const uint32_t Cu = (uint32_t)C;
+  for (uint32_t base = 0, par = 0; base < Cu; base += TPB * TOPK_ITEMS, par ^= 1) {
+    const uint32_t c0 = base + t * TOPK_ITEMS;
+    uint32_t key[TOPK_ITEMS], mine = 0;                   // mine: #(key > T) in the low half, #(key == T) in the high half (<= 1024 per chunk)
+#pragma unroll
+    for (int i = 0; i < TOPK_ITEMS; ++i) {
+      const bool in = c0 + i < Cu;
+      key[i] = in ? topk_key(x[c0 + i]) : 0u;
+      mine += (in && key[i] > T) ? 1u : 0u;
+      mine += (in && key[i] == T) ? 0x10000u : 0u;
+    }
+    uint32_t inc = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t up = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += up;
+    }
+    if (lane == 63) wtot[par][w] = inc;                    // double-buffered: one barrier per chunk
+    __syncthreads();
+    uint32_t before = inc - mine, all = 0;
+#pragma unroll
+    for (int i = 0; i < TPB / 64; ++i) {
+      const uint32_t v = wtot[par][i];
+      before += i < w ? v : 0u;
+      all += v;
+    }
+    uint32_t gpos = gtot + (before & 0xffffu), epos = etot + (before >> 16);
+#pragma unroll
+    for (int i = 0; i < TOPK_ITEMS; ++i) {
+      const bool in = c0 + i < Cu;
+      if (in && key[i] > T) {
+        if (gpos < G) { ckey[gpos] = key[i]; cidx[gpos] = (int)(c0 + i); }
+        ++gpos;
+      } else if (in && key[i] == T) {
+        if (epos < need) { ckey[G + epos] = key[i]; cidx[G + epos] = (int)(c0 + i); }
+        ++epos;
+      }
+    }
+    gtot += all & 0xffffu;
+    etot += all >> 16;
+    if (gtot >= G && etot >= need) break;                 // the same totals in every thread: a uniform exit
+  }
+  __syncthreads();
+  if (t < k) {
+    const uint32_t kj = ckey[t];
+    const int ij = cidx[t];
+    int place = 0;
+    for (int i = 0; i < k; ++i) place += (ckey[i] > kj || (ckey[i] == kj && cidx[i] < ij)) ? 1 : 0;
+    values[(long long)r * k + place] = lg[(long long)r * ld + ij];
+    indices[(long long)r * k + place] = ij;
+  }
+}
+
 // cosine similarity pieces (F.cosine_similarity eps = 1e-8 clamps each norm)
 struct Cos { float dot, na, nb; };
 __device__ __forceinline__ Cos cos_parts(const float* a, const float* b, int H, float* sh) {
@@ -256,6 +352,15 @@ extern "C" int mart_lsce_bwd(const float* logits, int ld, const int64_t* label, 
 extern "C" int mart_rank(const float* logits, int ld, const int64_t* label, int64_t* rank, int R, int C, void* stream) {
   MART_CHECK(logits && label && rank && R > 0 && C > 0 && ld >= C, "rank: bad args");
   hipLaunchKernelGGL(rank_k, dim3(R), dim3(TPB), 0, (hipStream_t)stream, logits, ld, label, rank, R, C);
+  MART_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int mart_topk(const float* logits, int ld, int R, int C, int k, float* values, int32_t* indices, void* stream) {
+  MART_CHECK(logits && values && indices, "topk: null pointer");
+  MART_CHECK(R >= 1 && C >= 1 && ld >= C, "topk: needs R >= 1, C >= 1 and ld >= C");
+  MART_CHECK(k >= 1 && k <= TOPK_MAX, "topk: k must be in [1, 64]");
+  MART_CHECK(k <= C, "topk: k exceeds the row length C");
+  hipLaunchKernelGGL(topk_k, dim3(R), dim3(TPB), 0, (hipStream_t)stream, logits, ld, C, k, values, indices);
   MART_LAUNCH_CHECK();
   return 0;
 }

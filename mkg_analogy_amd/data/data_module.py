@@ -235,6 +235,45 @@ class KGC(BaseDataModule):
     def get_config(self) -> Dict[str, Any]:
         return {k: v for k, v in self.__dict__.items() if "st" in k or "ed" in k or "analogy" in k}    # :245-251
 
+    # ---- label-space index -> key and text (the inverse of the processor's tables; what a prediction is read with).  Nothing is kept on the
+    # instance: get_config() hands every attribute whose name contains "st", "ed" or "analogy" to the lit model.
+    @staticmethod
+    def _describe(indices, keys: List[str], text: Dict[str, str], what: str) -> List[Dict[str, Any]]:
+        flat = torch.as_tensor(indices).reshape(-1).tolist() if not isinstance(indices, (list, tuple)) else list(indices)
+        out = []
+        for i in flat:
+            i = int(i)
+            if not 0 <= i < len(keys):
+                raise IndexError(f"{what} index {i} outside [0, {len(keys)})")
+            out.append({"index": i, "key": keys[i], "text": text[keys[i]]})
+        return out
+
+    def describe_entities(self, indices, space: str = "analogy") -> List[Dict[str, Any]]:
+        """``[{"index", "key", "text"}]`` for label-space entity indices (a flat list, array or tensor; ``predict_step``'s ``entity_topk`` row).
+        ``space="analogy"``: the position in ``analogy_entity_ids`` (fine-tune labels, the inverse of ``analogy_ent2id``); ``space="entity"``: the
+        position in the entity file, i.e. inside ``entity_id_st:entity_id_ed`` (pre-train labels, the inverse of ``ent2id``)."""
+        t = self.processor.tables(self.args.data_dir)
+        if space == "analogy":
+            keys = list(t.analogy_ent2id)
+        elif space == "entity":
+            keys = list(t.ent2id)
+        else:
+            raise ValueError(f"space must be 'analogy' or 'entity', got {space!r}")
+        return self._describe(indices, keys, t.ent2text, "entity")
+
+    def describe_relations(self, indices, space: str = "analogy") -> List[Dict[str, Any]]:
+        """The same for relations.  ``space="relation"``: the position in the relation file, i.e. inside ``relation_id_st:relation_id_ed`` (what
+        ``predict_step``'s ``relation_topk`` holds); ``space="analogy"``: the position in ``analogy_relation_ids`` (the numbering ``rel2id`` gives the
+        analogy relations, processor.py:639-643)."""
+        t = self.processor.tables(self.args.data_dir)
+        keys = list(t.rel2text)
+        if space == "analogy":
+            chosen = set(self.processor.get_analogy_relations(self.args.data_dir))
+            keys = [r for i, r in enumerate(keys) if f"[RELATION_{i}]" in chosen]
+        elif space != "relation":
+            raise ValueError(f"space must be 'analogy' or 'relation', got {space!r}")
+        return self._describe(indices, keys, t.rel2text, "relation")
+
     @staticmethod
     def add_to_argparse(parser):
         BaseDataModule.add_to_argparse(parser)

@@ -295,6 +295,44 @@ def entity_ranks(logits: torch.Tensor, label: torch.Tensor) -> torch.Tensor:
     return out
 
 
+TOPK_MAX = 64          # mart_topk's candidate list lives in LDS
+
+
+def _topk_i32(logits: torch.Tensor, k: int):
+    """(values f32 [R, k], indices int32 [R, k]) as mart_topk writes them; the checks run on the host before anything is launched."""
+    if not torch.is_tensor(logits) or logits.dim() != 2:
+        raise ValueError("topk: logits must be a 2-D tensor [rows, columns]")
+    if logits.dtype != F32:
+        raise ValueError(f"topk: logits must be float32, got {logits.dtype}")
+    k = int(k)
+    R, C = logits.shape
+    if k < 1 or k > TOPK_MAX:
+        raise ValueError(f"topk: k must be in [1, {TOPK_MAX}], got {k}")
+    if k > C:
+        raise ValueError(f"topk: k = {k} exceeds the {C} scored columns")
+    if R < 1:
+        raise ValueError("topk: no rows")
+    if not logits.is_cuda:
+        raise ValueError("topk: logits must live on the HIP device (there is no CPU path)")
+    logits = logits.detach()
+    if logits.stride(1) != 1 or logits.stride(0) < C:         # (a transposed or broadcast view: the only case that copies)
+        logits = logits.contiguous()
+    values = torch.empty((R, k), device=logits.device, dtype=F32)
+    indices = torch.empty((R, k), device=logits.device, dtype=torch.int32)
+    ops.topk(logits, k, values, indices)
+    return values, indices
+
+
+def topk(logits: torch.Tensor, k: int):
+    """The k best columns of every row of a 2-D fp32 device tensor: (values f32 [R, k], indices int64 [R, k]), the first k columns of
+    ``torch.sort(logits, dim=1, descending=True, stable=True)`` -- values descend, equal values in ascending index order, NaN before +inf
+    (include/mart_hip.h: mart_topk).  A row stride other than C is passed on as the leading dimension, without a copy; nothing syncs with the host.
+    The kernel writes int32 indices: widening them to the int64 torch callers index with is this function's one elementwise launch
+    (predict_step widens on the host instead)."""
+    values, indices = _topk_i32(logits, k)
+    return values, indices.to(torch.int64)
+
+
 class LazyRows:
     """``logits[arange(B), mask_idx]`` without the [B,L,V] tensor; supports ``[:, ids]``, ``[rows, st:ed]``, ``[rows, ids]``."""
 

@@ -148,22 +148,24 @@ class TransformerLitModel(BaseLitModel):
         mask_logits = rows[:, self._ids("analogy_entity_ids")]
         return dict(entity_ranks=Fn.entity_ranks(mask_logits, label).cpu().numpy())
 
-    def _eval_at(self, batch, batch_idx):
-        """Validation / test batches are scored on the fp32-accurate path (engine_precise) by default: the reference evaluates in fp32 and the
+    def _eval_at(self, batch, batch_idx, step=None, **kw):
+        """Validation / test / predict batches are scored on the fp32-accurate path (engine_precise) by default: the reference evaluates in fp32 and the
         acceptance criterion for this step is bit-exact ranked entity indices (lit_models/transformer.py:162-164), which a bf16 forward can only
         meet where the margin exceeds its logit error.  3.3 x the time of a bf16 evaluation pass (2.4 k against 8 k examples/s on one MI355X).
-        ``args.eval_precision = "bf16"`` (or MART_EVAL_PRECISION=bf16) evaluates in the training configuration."""
+        ``args.eval_precision = "bf16"`` (or MART_EVAL_PRECISION=bf16) evaluates in the training configuration.  ``step``: the hook body run under the
+        switch (default ``_eval``; ``predict_step`` passes ``_predict``)."""
         import os
+        step = self._eval if step is None else step
         prec = getattr(self.args, "eval_precision", None) or os.environ.get("MART_EVAL_PRECISION", "fp32")
         if not hasattr(self.model, "set_precision"):
             prec = None
         cur = getattr(self.model, "precision", "bf16")
         if not prec or prec == cur:
-            return self._eval(batch, batch_idx)
+            return step(batch, batch_idx, **kw)
         old = cur
         self.model.set_precision(prec)
         try:
-            return self._eval(batch, batch_idx)
+            return step(batch, batch_idx, **kw)
         finally:
             self.model.set_precision(old)
 
@@ -172,6 +174,63 @@ class TransformerLitModel(BaseLitModel):
 
     def test_step(self, batch, batch_idx):
         return self._eval_at(batch, batch_idx)
+
+    # -- answering a query: the k best entities of (head, relation, ?).  No counterpart in the reference's lit model (pl.Trainer.predict would need
+    # one); the selection is mart_topk, in the order of the reference's descending stable sort (lit_models/transformer.py:162).
+    @torch.no_grad()
+    def _predict(self, batch, batch_idx, k=None):
+        k = int(getattr(self.args, "predict_topk", None) or 10) if k is None else int(k)
+        if k < 1:
+            raise ValueError(f"predict_step: k must be positive, got {k}")
+        label = batch.pop("label", None)
+        pre_type = batch.pop("pre_type", None)
+        for key in ("rel_idx", "rel_label", "q_head_idx", "a_head_idx"):
+            batch.pop(key, None)
+        if self.args.pretrain and "VisualBertKGC" in str(type(self.model)):
+            raise NotImplementedError("VisualBertKGC has no MarKG pre-train step on the HIP path (fine-tune only)")
+        input_ids = batch["input_ids"]
+        model_output = self.model(**batch, return_dict=True, **self._needed(input_ids, None))
+        logits = model_output[0].logits
+        dev = logits.trans.device
+        rows = self._mask_rows(logits, input_ids.to(dev))
+        if label is not None:
+            label = label.to(dev)
+
+        def best(lg, lab, name, out):
+            kk = min(k, Fn.TOPK_MAX, int(lg.shape[1]))           # clamped to the scored slice (and to the kernel's list length)
+            values, indices = Fn._topk_i32(lg, kk)
+            ranks = Fn.entity_ranks(lg, lab) if lab is not None else None     # the same logits: the model ran once, the [MASK] rows were scored once
+            out[f"{name}_topk"] = indices.cpu().numpy().astype(np.int64)
+            out[f"{name}_topk_logits"] = values.cpu().numpy()
+            if ranks is not None:
+                out[f"{name}_ranks"] = ranks.cpu().numpy()
+
+        out = {}
+        if self.args.pretrain:
+            if pre_type is None:
+                raise ValueError("predict_step in pre-train mode needs pre_type (which examples ask for an entity, which for a relation)")
+            pre_type = pre_type.to(dev)
+            for name, sel, st, ed in (("entity", pre_type != 2, self.entity_id_st, self.entity_id_ed),
+                                      ("relation", pre_type == 2, self.relation_id_st, self.relation_id_ed)):
+                idx = sel.nonzero(as_tuple=True)[0]
+                if len(idx) > 0:
+                    out[f"{name}_rows"] = idx.cpu().numpy()
+                    best(rows[idx, st:ed], None if label is None else label[idx], name, out)
+            if not out:
+                raise ValueError("entity and relation cannot be None at the same time.")
+            return out
+        best(rows[:, self._ids("analogy_entity_ids")], label, "entity", out)
+        return out
+
+    def predict_step(self, batch, batch_idx, k=None):
+        """The ``k`` best answers of every example, as host numpy arrays (``k``: ``args.predict_topk`` if present, else 10; clamped to the scored
+        slice).  ``label`` is optional: with it the ranks of ``validation_step`` ride along, from the same logits.
+        Fine-tune: ``entity_topk`` int64 [B, k] in the label's index space (positions in ``analogy_entity_ids``; ``KGC.describe_entities`` names
+        them), ``entity_topk_logits`` float32 [B, k], ``entity_ranks`` [B] with labels.  Pre-train: ``entity_rows`` / ``relation_rows`` (batch
+        positions by ``pre_type``), ``entity_topk`` / ``relation_topk`` (indices inside the entity / relation slice), ``*_topk_logits`` and, with
+        labels, ``*_ranks``.  Lists come in the order of a descending stable sort: equal logits by ascending index, a NaN logit first.
+        Same precision switch as ``validation_step``; ``Fn.check_status()`` reports an example without [MASK] as there."""
+        return self._eval_at(batch, batch_idx, step=self._predict, k=k)
 
     # -- lit_models/transformer.py:173-222
     def _epoch_end(self, outputs):

@@ -386,6 +386,12 @@ def rank(logits, label, out):
     L.check(L.lib().mart_rank(_p(logits), _rows2d(logits), _p(label), _p(out), R, Cc, _stream()), "mart_rank")
 
 
+def topk(logits, k, values, indices):
+    """values f32 [R, k] / indices int32 [R, k]: the first k columns of the stable descending sort of every row (include/mart_hip.h: mart_topk)."""
+    R, Cc = logits.shape
+    L.check(L.lib().mart_topk(_p(logits), _rows2d(logits) if R > 1 else Cc, R, Cc, int(k), _p(values), _p(indices), _stream()), "mart_topk")
+
+
 def simloss_fwd(trans, rel_idx, q_idx, a_idx, loss_rows, rows=None, L_=None):
     """``rows`` (int32 [B, nr] flat ids) given: ``trans`` is the compact [B * nr, H] tensor of a row-subset pass and ``L_`` the sequence length."""
     if rows is None:

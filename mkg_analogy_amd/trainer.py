@@ -175,6 +175,22 @@ class Trainer:
         end_fn([merged])
         return dict(lit.logged)
 
+    def predict(self, lit, batches, k: Optional[int] = None) -> Dict[str, "np.ndarray"]:
+        """``lit.predict_step`` over ``batches`` in eval mode: one dict with the per-batch arrays concatenated in loader order.  ``*_rows`` (pre-train:
+        which examples asked for an entity, which for a relation) are offset by the examples seen before, so they index the concatenated loader,
+        not a batch.  Under a sharded loader every rank gets the predictions of ITS shard: nothing is gathered."""
+        import numpy as np
+        lit.model.eval()
+        parts: Dict[str, list] = {}
+        seen = 0
+        for i, b in enumerate(batches):
+            out = lit.predict_step(dict(b), i, k=k)
+            for key, v in out.items():
+                parts.setdefault(key, []).append(v + seen if key.endswith("_rows") else v)
+            seen += int(b["input_ids"].shape[0])
+        Fn.check_status()                                          # an example without [MASK] (one host sync for the whole pass)
+        return {key: np.concatenate(v) for key, v in parts.items()}
+
     def validate(self, lit, batches) -> Dict[str, float]:
         return self._run_eval(lit, batches, lit.validation_step, lit.validation_epoch_end)
 
