@@ -11,7 +11,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libmart_hip.so")
-SOURCES = ["util.hip", "gemm_nt.hip", "gemm_tn.hip", "norm_embed.hip", "attention.hip", "fusion.hip", "head_optim.hip", "precise.hip", "vilt.hip", "visual_bert.hip"]
+SOURCES = ["util.hip", "gemm_nt.hip", "gemm_tn.hip", "norm_embed.hip", "attention.hip", "fusion.hip", "head_optim.hip", "precise.hip", "vilt.hip", "visual_bert.hip", "grad_clip.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # per-file extras: attention keeps MFMA results in arch VGPRs (the softmax consumes them with VALU right away; the
 # default AGPR form cost ~150 v_accvgpr moves per 16 MFMAs)
@@ -31,7 +31,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(ROOT, "include", "mart_hip.h")]
+    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(ROOT, "include", "mart_hip.h"), os.path.join(ROOT, "include", "mart_clip.h")]
     jobs = []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

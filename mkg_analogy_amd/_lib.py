@@ -189,6 +189,14 @@ _SIGS = {
     "mart_vbert_embed_bwd": (i32, [C.POINTER(VbertEmbed), vp]),
 }
 
+# include/mart_clip.h: gradient clipping / norm tracking, an addition beside the C ABI above (not part of EXPORTS, no ABI bump)
+_CLIP_SIGS = {
+    "mart_clip_partials_needed": (i32, [i32]),
+    "mart_clip_sumsq": (i32, [vp, vp, i32, i32, vp, i32, vp]),
+    "mart_clip_finalize": (i32, [vp, i32, i32, f32, f32, vp, vp, i32, vp]),
+    "mart_clip_apply": (i32, [vp, vp, i32, vp, f32, vp]),
+}
+
 EXPORTS = tuple(_SIGS)
 EXPECTED_ABI = 10           # the layout the ctypes structures above were written for (mart_abi_version() of the library must match)
 _lib = None
@@ -202,7 +210,7 @@ def lib():
             raise MartError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                             "(the MKGformer path has no non-HIP fallback)")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_CLIP_SIGS.items()):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args

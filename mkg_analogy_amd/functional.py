@@ -333,6 +333,56 @@ def topk(logits: torch.Tensor, k: int):
     return values, indices.to(torch.int64)
 
 
+def _clip_store(model_or_store):
+    """The FlatStore behind a model (``model.store``) or the store itself, on the HIP device."""
+    store = getattr(model_or_store, "store", model_or_store)
+    if not hasattr(store, "chunks") or not hasattr(store, "grad"):
+        raise ValueError("clip: needs a model with a flat parameter store (model.store) or the store itself")
+    if not store.grad.is_cuda:
+        raise ValueError("clip: the gradient buffer must live on the HIP device (there is no CPU path)")
+    return store
+
+
+def _grad_norm(store, mode: int, grad_scale: float, max_norm: float) -> torch.Tensor:
+    """(norm, coef) on the device for the live chunks of ``store.grad`` (include/mart_clip.h); nothing syncs with the host."""
+    partials = torch.empty(ops.clip_partials_needed(store.n_chunks), device=store.grad.device, dtype=torch.float64)
+    out = torch.empty(2, device=store.grad.device, dtype=F32)
+    ops.clip_sumsq(store.grad, store.chunks, store.n_chunks, mode, partials)
+    ops.clip_finalize(partials, mode, out, grad_scale=float(grad_scale), max_norm=float(max_norm))
+    return out
+
+
+def grad_norm(model_or_store, norm_type=2.0, grad_scale: float = 1.0) -> torch.Tensor:
+    """``grad_scale`` x the 2- or inf-norm of the gradients of the trainable parameters taken together (the AdamW chunk table: frozen and dead tensors
+    take no part, as tensors whose grad is None in torch), as a device fp32 scalar.  Accumulated in float64; bit-identical from run to run."""
+    from .optim import norm_mode
+    mode = norm_mode(norm_type)                            # refused before the device is looked at
+    return _grad_norm(_clip_store(model_or_store), mode, grad_scale, 0.0)[0]
+
+
+def clip_grad_norm_(model_or_store, max_norm: float, norm_type=2.0, grad_scale: float = 1.0) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` on the flat gradient buffer: the gradients are multiplied by min(1, max_norm / (norm + 1e-6)), decided
+    and applied on the device (a clip that does not trigger writes nothing).  Returns the norm before clipping, a device scalar.  ``grad_scale``: the factor the
+    optimizer applies to the buffer later (``optimizer.grad_scale``); the norm is that of the scaled gradients."""
+    from .optim import norm_mode
+    mode = norm_mode(norm_type)
+    if not float(max_norm) > 0.0:
+        raise ValueError(f"clip: max_norm must be positive, got {max_norm!r}")
+    store = _clip_store(model_or_store)
+    out = _grad_norm(store, mode, grad_scale, max_norm)
+    ops.clip_apply(store.grad, store.chunks, store.n_chunks, coef=out[1:])
+    return out[0]
+
+
+def clip_grad_value_(model_or_store, clip_value: float, grad_scale: float = 1.0) -> None:
+    """``torch.nn.utils.clip_grad_value_``: every gradient element of the trainable parameters is clamped so that ``grad_scale`` x it lies in
+    [-clip_value, clip_value] (NaN stays NaN)."""
+    if not float(clip_value) > 0.0 or not float(grad_scale) > 0.0:
+        raise ValueError(f"clip: clip_value and grad_scale must be positive, got {clip_value!r}, {grad_scale!r}")
+    store = _clip_store(model_or_store)
+    ops.clip_apply(store.grad, store.chunks, store.n_chunks, clip_value=float(clip_value) / float(grad_scale))
+
+
 class LazyRows:
     """``logits[arange(B), mask_idx]`` without the [B,L,V] tensor; supports ``[:, ids]``, ``[rows, st:ed]``, ``[rows, ids]``."""
 

@@ -45,6 +45,16 @@ class BaseLitModel(LightningModuleLite):
         parser.add_argument("--optimizer", type=str, default=OPTIMIZER, help="optimizer class (AdamW is the fused HIP implementation)")
         parser.add_argument("--lr", type=float, default=LR)
         parser.add_argument("--weight_decay", type=float, default=0.01)
+        # pl.Trainer.add_argparse_args supplies these three in the reference (main.py:25); without pytorch_lightning they come from here, for
+        # mkg_analogy_amd.trainer.Trainer(gradient_clip_val=..., gradient_clip_algorithm=..., track_grad_norm=...)
+        have = getattr(parser, "_option_string_actions", {})
+        if "--gradient_clip_val" not in have:
+            parser.add_argument("--gradient_clip_val", type=float, default=None, help="clip the gradients to this 2-norm (or value); None / 0: off")
+        if "--gradient_clip_algorithm" not in have:
+            parser.add_argument("--gradient_clip_algorithm", type=str, default="norm", choices=("norm", "value"))
+        if "--track_grad_norm" not in have:
+            parser.add_argument("--track_grad_norm", type=lambda v: v if v == "inf" else int(float(v)), default=None,
+                                help="2 or inf: log that norm of the gradients every optimizer step")
         return parser
 
     def forward(self, x):

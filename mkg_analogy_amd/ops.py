@@ -508,6 +508,34 @@ def adamw(*, master, grad, m, v, shadow, chunks, n_chunks, lr, beta1, beta2, eps
     L.check(L.lib().mart_adamw(C.byref(d), _stream()), "mart_adamw")
 
 
+# ---------------------------------------------------------------- gradient clipping / norm tracking (include/mart_clip.h, csrc/grad_clip.hip)
+CLIP_NORM_2, CLIP_NORM_INF = 0, 1
+
+
+def clip_partials_needed(n_chunks: int) -> int:
+    """Elements of the float64 ``partials`` buffer clip_sumsq needs for a chunk table of ``n_chunks`` rows (host arithmetic, no launch)."""
+    n = int(L.lib().mart_clip_partials_needed(int(n_chunks)))
+    if n < 0:
+        L.check(n, "mart_clip_partials_needed")
+    return n
+
+
+def clip_sumsq(grad, chunks, n_chunks, mode, partials):
+    """partials (float64) <- per-work-item sum of g^2 (mode 0) or max |g| (mode 1) over the live chunks of the table."""
+    L.check(L.lib().mart_clip_sumsq(_p(grad), _p(chunks), int(n_chunks), int(mode), _p(partials), partials.numel(), _stream()), "mart_clip_sumsq")
+
+
+def clip_finalize(partials, mode, out, *, grad_scale=1.0, max_norm=0.0, log=None, log_index=0):
+    """out[0] = grad_scale * norm, out[1] = min(1, max_norm / (out[0] + 1e-6)) (1 when max_norm <= 0); log[log_index] = out[0] when ``log`` is given."""
+    L.check(L.lib().mart_clip_finalize(_p(partials), partials.numel(), int(mode), float(grad_scale), float(max_norm), _p(out), _p(log), int(log_index),
+                                       _stream()), "mart_clip_finalize")
+
+
+def clip_apply(grad, chunks, n_chunks, coef=None, clip_value=0.0):
+    """clip_value <= 0: g *= coef[0] on the live chunks (nothing is touched when it is exactly 1); clip_value > 0: g = clamp(g, -clip_value, clip_value)."""
+    L.check(L.lib().mart_clip_apply(_p(grad), _p(chunks), int(n_chunks), _p(coef), float(clip_value), _stream()), "mart_clip_apply")
+
+
 def block_table(src, dst, table, n):
     L.check(L.lib().mart_block_table(_p(src), _p(dst), _p(table), n, _stream()), "mart_block_table")
 

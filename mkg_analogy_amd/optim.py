@@ -2,7 +2,9 @@
 (reference: lit_models/transformer.py:224-241; torch.optim.AdamW and HF get_linear_schedule_with_warmup semantics)."""
 from __future__ import annotations
 
+import math
 import os
+from typing import Optional
 
 import torch
 
@@ -10,7 +12,138 @@ from . import ops
 from .params import NO_DECAY, check_layout, layout_list
 
 
-class FusedAdamW(torch.optim.Optimizer):
+def norm_mode(norm_type) -> int:
+    """``2`` / ``2.0`` / ``"2"`` -> ops.CLIP_NORM_2, ``inf`` / ``"inf"`` -> ops.CLIP_NORM_INF: the two norms the clip kernels compute."""
+    try:
+        v = float(norm_type)
+    except (TypeError, ValueError):
+        v = None
+    if v == 2.0:
+        return ops.CLIP_NORM_2
+    if v == math.inf:
+        return ops.CLIP_NORM_INF
+    raise ValueError(f"clip: norm_type must be 2 or inf, got {norm_type!r}")
+
+
+class GradClip:
+    """pl.Trainer's ``gradient_clip_val`` / ``gradient_clip_algorithm`` / ``track_grad_norm`` on the flat gradient buffer, as kernels that run between
+    the backward pass and the AdamW launch (include/mart_clip.h): per norm one streaming pass into float64 partials and a one-workgroup finalize that
+    leaves (norm, clip coefficient) on the device, then one pass that scales -- and returns at once when the coefficient is 1 -- or clamps.  The
+    chunk table says which elements are gradients of trainable parameters.  Nothing here synchronises with the host, and every buffer (partials, one
+    (norm, coef) pair and one log row of ``log_slots`` steps per norm) is allocated here, once.
+
+    ``clip_val`` None or <= 0: no clipping (PL).  ``algorithm`` "norm": the 2-norm of all gradients together is brought down to ``clip_val``;
+    "value": every element is clamped to +-``clip_val``.  ``track_norm`` 2 / "inf" / None: the norm to report (before clipping, as PL); a tracked
+    2-norm and norm clipping share their pass."""
+
+    def __init__(self, store, clip_val=None, algorithm: str = "norm", track_norm=None, log_slots: int = 1024):
+        if algorithm not in ("norm", "value"):
+            raise ValueError(f"clip: gradient_clip_algorithm must be 'norm' or 'value', got {algorithm!r}")
+        self.clip_val = float(clip_val) if clip_val is not None and float(clip_val) > 0 else None
+        self.algorithm = algorithm
+        self.track_mode = None if track_norm is None else norm_mode(track_norm)
+        by_norm = self.clip_val is not None and algorithm == "norm"
+        self.passes = []                                             # (mode, max_norm): one sumsq + finalize each; max_norm 0 = track only
+        self.i_track = self.i_clip = None
+        if self.track_mode is not None and not (by_norm and self.track_mode == ops.CLIP_NORM_2):
+            self.i_track = len(self.passes)
+            self.passes.append((self.track_mode, 0.0))
+        if by_norm:
+            self.i_clip = len(self.passes)
+            self.passes.append((ops.CLIP_NORM_2, self.clip_val))
+            if self.track_mode == ops.CLIP_NORM_2:
+                self.i_track = self.i_clip
+        self.active = self.clip_val is not None or self.track_mode is not None
+        dev = store.grad.device
+        self.log_slots = max(1, int(log_slots))
+        self.log_index = 0
+        self.partials = torch.zeros(ops.clip_partials_needed(max(1, store.n_chunks)), device=dev, dtype=torch.float64)
+        self._n_chunks = store.n_chunks
+        self.outs = torch.zeros(max(1, len(self.passes)), 2, device=dev, dtype=torch.float32)
+        self.logs = torch.zeros(max(1, len(self.passes)), self.log_slots, device=dev, dtype=torch.float32)
+
+    def plan(self, grad_scale: float = 1.0) -> dict:
+        """What one step launches (pure host logic): the norm passes, and how the gradients are changed.  The buffer holds the unscaled sum
+        and AdamW multiplies by ``grad_scale`` later, so the norm is scaled in the finalize and a value threshold is divided by it:
+        clamp(s g, +-v) = s clamp(g, +-v / s)."""
+        by_value = self.clip_val is not None and self.algorithm == "value"
+        return {"passes": list(self.passes), "apply": "norm" if self.i_clip is not None else "value" if by_value else None,
+                "clip_value": self.clip_val / float(grad_scale) if by_value else 0.0}
+
+    def run(self, store, grad_scale: float = 1.0) -> None:
+        if not store.grad.is_cuda:
+            raise ValueError("clip: the gradient buffer must live on the HIP device (there is no CPU path)")
+        n = store.n_chunks
+        if n != self._n_chunks:                                      # the chunk table was rebuilt: more rows (a thaw) is the one case that allocates
+            if ops.clip_partials_needed(n) > self.partials.numel():
+                self.partials = torch.zeros(ops.clip_partials_needed(n), device=store.grad.device, dtype=torch.float64)
+            self._n_chunks = n
+        plan = self.plan(grad_scale)
+        slot = self.log_index if self.log_index < self.log_slots else None          # a full log stops recording
+        for i, (mode, max_norm) in enumerate(plan["passes"]):
+            ops.clip_sumsq(store.grad, store.chunks, n, mode, self.partials)
+            ops.clip_finalize(self.partials, mode, self.outs[i], grad_scale=grad_scale, max_norm=max_norm,
+                              log=None if slot is None else self.logs[i], log_index=slot or 0)
+        if plan["apply"] == "norm":
+            ops.clip_apply(store.grad, store.chunks, n, coef=self.outs[self.i_clip, 1:])
+        elif plan["apply"] == "value":
+            ops.clip_apply(store.grad, store.chunks, n, clip_value=plan["clip_value"])
+        self.log_index += 1
+
+    @property
+    def last_norm(self):
+        """Device scalar: the tracked norm of the last step, or the clip's 2-norm when nothing else is tracked (None: value clipping alone)."""
+        i = self.i_track if self.i_track is not None else self.i_clip
+        return None if i is None else self.outs[i, 0]
+
+    @property
+    def last_coef(self):
+        """Device scalar: the factor the last step's gradients were multiplied by (1: the clip did not trigger; None without norm clipping)."""
+        return None if self.i_clip is None else self.outs[self.i_clip, 1]
+
+    def read_log(self, reset: bool = True):
+        """(norms, clipped_steps) of the steps since the last reset: one device-to-host copy (the only synchronisation, at a place the caller
+        chooses).  ``norms``: float32 numpy array, one entry per step (None when no norm is computed); ``clipped_steps``: steps whose clip
+        coefficient -- recomputed from the logged norm with the kernel's fp32 expression -- was below 1 (None without norm clipping)."""
+        import numpy as np
+        n = min(self.log_index, self.log_slots)
+        logs = self.logs[:, :n].cpu().numpy()
+        if reset:
+            self.log_index = 0
+        i = self.i_track if self.i_track is not None else self.i_clip
+        norms = None if i is None else logs[i].copy()
+        clipped = None
+        if self.i_clip is not None:
+            with np.errstate(all="ignore"):
+                coef = (np.float32(1.0) / (logs[self.i_clip] + np.float32(1e-6))) * np.float32(self.clip_val)
+            clipped = int((coef < 1).sum())
+        return norms, clipped
+
+
+class _ClipsGradients:
+    """``set_grad_clip`` and the two device scalars of the optimizers that own a FlatStore."""
+    _clip: Optional[GradClip] = None
+
+    def set_grad_clip(self, clip_val=None, algorithm: str = "norm", track_norm=None, log_slots: int = 1024) -> None:
+        """Clip (and / or report the norm of) the gradients inside every ``step()``, before the update: see :class:`GradClip`.  With neither
+        ``clip_val`` nor ``track_norm`` the step is again exactly the unclipped one."""
+        gc = GradClip(self.model.store, clip_val, algorithm, track_norm, log_slots)
+        self._clip = gc if gc.active else None
+
+    def read_norm_log(self, reset: bool = True):
+        """(norms, clipped_steps) of the optimizer steps since the last reset (GradClip.read_log: one device-to-host copy); (None, None) when off."""
+        return (None, None) if self._clip is None else self._clip.read_log(reset)
+
+    @property
+    def last_grad_norm(self):
+        return None if self._clip is None else self._clip.last_norm
+
+    @property
+    def last_clip_coef(self):
+        return None if self._clip is None else self._clip.last_coef
+
+
+class FusedAdamW(torch.optim.Optimizer, _ClipsGradients):
     """One multi-tensor HIP launch per step: fp32 master/m/v update + bf16 shadow refresh, then W^T shadows.
 
     ``param_groups`` mirrors the reference's two groups (decay 0.01 / 0 by the substring rule) for inspection and
@@ -124,6 +257,15 @@ class FusedAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None):
         store = self.model.store
+        if self._clip is not None:
+            # the norm is global: every gradient must be final, and no weight may have moved, before the first update -- so the step is not
+            # streamed under the backward pass (the Trainer does not call begin_step() / ready() then) and the one launch below covers all chunks
+            if getattr(self, "_streaming", False) and self._cursor > 0:
+                raise RuntimeError("gradient clipping / norm tracking is set (set_grad_clip) but part of this step was already applied by ready(): "
+                                   "a global norm cannot be applied to weights that have moved -- do not stream the update (begin_step / ready)")
+            if not getattr(self, "_streaming", False):
+                self.begin_step()
+            self._clip.run(store, self.grad_scale)                        # current stream: after the backward pass, before the update (ready() orders the side stream behind it)
         if not getattr(self, "_streaming", False):
             self.begin_step()
         self.ready(store.total)                                           # whatever the backward pass did not release
@@ -161,7 +303,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self._schedule.load_state_dict(sd["scheduler"])
 
 
-class TorchOptimizerOnStore:
+class TorchOptimizerOnStore(_ClipsGradients):
     """Any other ``torch.optim`` class by name, as the reference allows (lit_models/base.py:31 ``getattr(torch.optim, optimizer)``;
     lit_models/transformer.py:224-232: the same two weight-decay groups, ``lr``, ``eps=1e-8`` -- so, as there, only classes that take ``eps``).
     The update is torch's own (its kernels, on the fp32 master views: ``p`` / ``p.grad`` are views of FlatStore.master / .grad); afterwards the
@@ -193,6 +335,8 @@ class TorchOptimizerOnStore:
             raise RuntimeError("the model's parameter storage was rebuilt (resize/.to()) after the optimizer was created")
         if self.grad_scale != 1.0:
             store.grad.mul_(self.grad_scale)                   # 1 / world (DDP mean) and 1 / accumulation windows
+        if self._clip is not None:
+            self._clip.run(store, 1.0)                         # the gradients are scaled already
         self.inner.step()
         store.refresh_shadows()
 

@@ -15,7 +15,13 @@ from .distributed import GradSync, all_gather_ranks
 
 class Trainer:
     def __init__(self, max_epochs: int = 1, max_steps: Optional[int] = None, accumulate_grad_batches: int = 1,
-                 world_size: Optional[int] = None, log_every: int = 0):
+                 world_size: Optional[int] = None, log_every: int = 0,
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm", track_grad_norm=None):
+        """``gradient_clip_val`` / ``gradient_clip_algorithm`` ("norm" | "value") / ``track_grad_norm`` (2 | "inf" | None): pl.Trainer's arguments of
+        those names.  With either set the optimizer clips / measures on the device inside ``step()`` (optim.GradClip) and the update is not streamed
+        under the backward pass (a global norm needs every gradient first): the ``MART_STREAM_OPT=0`` schedule.  Norms are logged on the device,
+        one slot per optimizer step, and read where the loop synchronises anyway: ``grad_norms`` (numpy, the last epoch) and the epoch's
+        ``history`` record."""
         self.max_epochs, self.max_steps, self.accumulate_grad_batches = max_epochs, max_steps, accumulate_grad_batches
         if world_size is None:                                      # one process per GPU under torchrun: the process group says how many
             import torch.distributed as dist
@@ -24,6 +30,17 @@ class Trainer:
         self.log_every = log_every
         import os
         self.stream_optimizer = os.environ.get("MART_STREAM_OPT", "1") == "1"   # AdamW ranges launched under the backward pass
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', got {gradient_clip_algorithm!r}")
+        if track_grad_norm is not None:
+            from .optim import norm_mode
+            norm_mode(track_grad_norm)                                 # 2 or "inf": refused here, not at the first step
+        self.gradient_clip_val = gradient_clip_val if gradient_clip_val is not None and float(gradient_clip_val) > 0 else None   # (PL: 0 is off)
+        self.gradient_clip_algorithm, self.track_grad_norm = gradient_clip_algorithm, track_grad_norm
+        self.clips_gradients = self.gradient_clip_val is not None or track_grad_norm is not None
+        if self.clips_gradients:
+            self.stream_optimizer = False                              # train_step then never calls begin_step() / routes ready(): one update after the clip
+        self.grad_norms = None                                         # numpy [optimizer steps] of the last epoch (fit)
         self.num_train_batches = 0
         self.global_step = 0
         self._steps_seen = 0
@@ -45,6 +62,12 @@ class Trainer:
             # this loop owns zero_grad() and step(): the update zeroes the gradients it consumes and the next zero_grad() skips its fill (optim.FusedAdamW)
             import os
             self.optimizer.fused_zero_grad = os.environ.get("MART_FUSED_ZERO_GRAD", "1") == "1"
+        if self.clips_gradients:
+            if not hasattr(self.optimizer, "set_grad_clip"):
+                raise RuntimeError(f"gradient_clip_val / track_grad_norm: {type(self.optimizer).__name__} has no set_grad_clip()")
+            acc = max(1, self.accumulate_grad_batches)
+            self.optimizer.set_grad_clip(self.gradient_clip_val, self.gradient_clip_algorithm, self.track_grad_norm,
+                                         log_slots=(len(train_batches) + acc - 1) // acc)          # one slot per optimizer step of an epoch
 
     @staticmethod
     def _shards(loader) -> int:
@@ -148,17 +171,33 @@ class Trainer:
                 loss = self.train_step(lit, batch, i, end_of_epoch=(i == n - 1))
                 if self.log_every and (i + 1) % self.log_every == 0:
                     Fn.check_status()
-                    print(f"epoch {epoch} step {i + 1}: loss {float(loss):.4f} lr {self.optimizer.param_groups[0]['lr']:.3e}")
+                    norm = getattr(self.optimizer, "last_grad_norm", None) if self.clips_gradients else None
+                    print(f"epoch {epoch} step {i + 1}: loss {float(loss):.4f} lr {self.optimizer.param_groups[0]['lr']:.3e}"
+                          + ("" if norm is None else f" grad_norm {float(norm):.4e}"))
                 if self.max_steps and self.global_step >= self.max_steps:
                     break
             Fn.check_status()                                      # bad labels / examples without [MASK] seen during the epoch (one host sync)
             rec = {"epoch": epoch, "train_time_s": time.time() - t0}
+            if self.clips_gradients:
+                rec.update(self.read_grad_norms())
             if val_batches is not None:
                 rec.update(self.validate(lit, val_batches))
             self.history.append(rec)
             if self.max_steps and self.global_step >= self.max_steps:
                 break
         return self.history
+
+    def read_grad_norms(self) -> Dict[str, float]:
+        """Copy the device-side norm log of the steps since the last call to the host (one synchronisation; ``fit`` calls this at the end of an
+        epoch, after check_status has synchronised anyway) and start a new one: ``grad_norms`` and the record entries made of it."""
+        norms, clipped = self.optimizer.read_norm_log(reset=True)
+        rec: Dict[str, float] = {}
+        self.grad_norms = norms
+        if norms is not None and len(norms):
+            rec["grad_norm_mean"], rec["grad_norm_max"] = float(norms.mean()), float(norms.max())
+        if clipped is not None:
+            rec["clipped_steps"] = clipped
+        return rec
 
     def _run_eval(self, lit, batches, step_fn, end_fn) -> Dict[str, float]:
         lit.model.eval()
