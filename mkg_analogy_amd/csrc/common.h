@@ -180,6 +180,14 @@ __device__ __forceinline__ float act_grad(float z, int act) {
   }
   return 1.0f;
 }
+// act'(z) accurate RELATIVE to its own value in the negative GELU tail: 0.5 (1 + erf(u)) carries an absolute 3e-8 from the cancellation, percents of
+// a derivative that is 1e-6 at z = -5 and that bf16 still represents down to z = -12; erfc has no cancellation there.  Below z = -4 only (there the
+// 3e-8 is still a tenth of a bf16 ulp of the derivative): above it the result is act_grad's, bit for bit.  For the stand-alone mart_act_bwd (one
+// [rows, H] tensor of the MLM head per step), not for the GEMM epilogues.
+__device__ __forceinline__ float act_grad_tail(float z, int act) {
+  if (act == ACT_GELU && z < -4.0f) return 0.5f * erfcf(z * -0.70710678118654752440f) + z * (0.39894228040143267794f * __expf(-0.5f * z * z));
+  return act_grad(z, act);
+}
 
 // ---- wave / block reductions
 __device__ __forceinline__ float wave_sum(float v) {

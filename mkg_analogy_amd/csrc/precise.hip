@@ -833,6 +833,7 @@ extern "C" int mart_attn_bwd_f32(const mart_attn_bwd_f32_desc* d, void* stream) 
   MART_CHECK(d->f.B > 0 && d->f.nh > 0 && d->f.Sq > 0 && d->f.Sk > 0 && d->f.Lp >= 0, "attn_bwd_f32: bad shape");
   MART_CHECK(d->f.ldq % 4 == 0 && d->f.ldk % 4 == 0 && d->f.ldv % 4 == 0 && (d->f.Lp == 0 || (d->f.pk && d->f.pv && d->dpk && d->dpv && d->f.ldp % 4 == 0)), "attn_bwd_f32: bad strides / prefix");
   MART_CHECK((d->f.w0 == nullptr) == (d->f.w1 == nullptr) && (!d->f.sep || (d->f.w0 && d->f.Lp == 0)), "attn_bwd_f32: reweight needs w0/w1 and no prefix");
+  MART_CHECK(!d->f.attn_mask || d->f.Lp == 0, "attn_bwd_f32: mask with prefix unsupported");
   MART_CHECK(d->f.rw_row_lo == 0, "attn_bwd_f32: rw_row_lo is not supported (ViLT has no fp32 training path)");
   if (d->f.D == 64) return launch_attn_bwd<64>(d, (hipStream_t)stream);
   if (d->f.D == 768) return launch_attn_bwd<768>(d, (hipStream_t)stream);

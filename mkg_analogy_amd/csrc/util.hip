@@ -195,10 +195,10 @@ __global__ void act_bwd_k(const bf16* __restrict__ dy, const bf16* __restrict__ 
   for (; i + 3 < n; i += stride) {
     f32x4 g = bf4_to_f4(*(const bf16x4*)(dy + i)), zz = bf4_to_f4(*(const bf16x4*)(z + i));
 #pragma unroll
-    for (int e = 0; e < 4; ++e) g[e] *= act_grad(zz[e], act);
+    for (int e = 0; e < 4; ++e) g[e] *= act_grad_tail(zz[e], act);
     *(bf16x4*)(o + i) = f4_to_bf4(g);
   }
-  if (i < n && i + 3 >= n) for (long long j = i; j < n; ++j) o[j] = f2bf(bf2f(dy[j]) * act_grad(bf2f(z[j]), act));
+  if (i < n && i + 3 >= n) for (long long j = i; j < n; ++j) o[j] = f2bf(bf2f(dy[j]) * act_grad_tail(bf2f(z[j]), act));
 }
 __global__ void scatter_add_rows_k(const float* __restrict__ src, const int32_t* __restrict__ rows, float* __restrict__ dst, int ld, int R, int H) {
   int r = blockIdx.x;

@@ -90,6 +90,31 @@ def test_integration_doc_stub_matches_binding(built):
     assert names == [f[0] for f in built.GemmNT._fields_]
 
 
+# entry points that compute nothing on the device: pure queries, exercised by every test that goes through the binding
+_NO_KERNEL_TEST = {
+    "mart_last_error": "returns the thread's last error string (read by every failed check)",
+    "mart_abi_version": "a constant, asserted at load time and in test_every_declared_symbol_is_exported_and_bound",
+    "mart_check_device": "device-name query behind ops.require_gpu(), the fixture of every kernel test",
+    "mart_ln_bwd_partials": "size query for the ln_bwd workspace (ops.ln_bwd calls it)",
+    "mart_gemm_tn_workspace_bytes": "size query for the gemm_tn workspace (ops.gemm_tn calls it)",
+}
+
+
+def test_every_entry_point_is_named_by_a_gpu_test():
+    """"Every C-ABI entry point against a plain reference of the same op" (tests/test_kernels_gpu.py) stays true: each entry of the two ctypes tables
+    is named in at least one tests/test_*_gpu.py, as mart_<name> or as a call ops.<name>( -- or stands in the short list of queries above."""
+    import glob
+    from mkg_analogy_amd import _lib
+    names = list(_lib._SIGS) + list(_lib._CLIP_SIGS)
+    assert len(names) == len(set(names)) >= 70
+    text = "\n".join(open(f).read() for f in sorted(glob.glob(os.path.join(ROOT, "tests", "test_*_gpu.py"))))
+    stale = sorted(set(_NO_KERNEL_TEST) - set(names))
+    assert not stale, f"exempt names that are no entry points any more: {stale}"
+    missing = [n for n in names if n not in _NO_KERNEL_TEST
+               and not re.search(r"\b" + n + r"\b", text) and not re.search(r"\bops\." + n[len("mart_"):] + r"\(", text)]
+    assert not missing, f"entry points that no GPU test names: {missing}"
+
+
 def test_product_fails_loudly_without_gpu(built):
     import torch
     if torch.cuda.is_available():
